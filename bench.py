@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — device-resident synthetic-payload GiB/s (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds everything else the line can carry, each a run of its own after
+the timed steps: the sampled check against the C oracle, the store-only
+reference shapes, the D2H-inclusive rate, the CPU baseline and configs 11-13's
+Python-loop rate (each still switched off by its --no-* option).
+--dump-outputs DIR writes what the last timed step left in the output ring
+(or the host buffers) as DIR/<name>.npy, float32, one row per 4 KiB block: the
+whole output when it fits 48 MiB of float32, else a fixed, seeded choice of
+its blocks.
 
 A "step" is one pass of the hot path over one batch: every object of the
 configuration generated once into HBM by the gfx950 kernel (src/data_gen.rs
@@ -28,9 +38,10 @@ reference's streaming callers (ObjectGen::fill_chunk at 64 KiB / 256 KiB /
 as BASELINE states it), not an 8 GiB sample.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including
-`roofline` (kernel-event timing vs the 8 TB/s HBM peak; the fill's store-only
-reference shapes beside it, which the fill beats) and `cpu_baseline` (the C
-port of the same generator on this host's cores — rank 0 at N=1 only).
+`roofline` (kernel-event timing of the timed steps vs the 8 TB/s HBM peak;
+with --full the fill's store-only reference shapes beside it, which the fill
+beats) and, with --full, `cpu_baseline` (the C port of the same generator on
+this host's cores — rank 0 at N=1 only).
 """
 from __future__ import annotations
 
@@ -156,6 +167,14 @@ def parse():
     p.add_argument("--batch-tile", type=int, default=None, help="batch tile blocks (1 = dense; default: per launch)")
     p.add_argument("--pace", type=int, default=None,
                    help="batch kernel wall-clock store floor in 10-ns ticks (0 = off; default: per launch)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run what the headline figure does not need: the check "
+                        "against the oracle, the store-only reference shapes, the D2H-inclusive rate, the CPU "
+                        "baseline and the single-buffer Python loop (each still subject to its --no-* option)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's output (the ring, or the host buffers) as DIR/<name>.npy, "
+                        "float32 rows of 4 KiB blocks: all of it up to 48 MiB of float32, else a fixed seeded "
+                        "choice of blocks (configs 18-21 call the unseeded entry point: their bytes differ per run)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--cpu-no-pin", action="store_true",
@@ -175,7 +194,10 @@ def parse():
                         "by the library, or pageable and page-locked by s3dg_host_register")
     p.add_argument("--device-override", type=int, default=None,
                    help="rehearsal only: put every rank on this device (e.g. 8 ranks on a 1-GPU box)")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:   # a plain run: set up, warm up, time the steps, print the line
+        args.no_verify = args.no_ceiling = args.no_d2h = args.no_cpu_baseline = True
+    return args
 
 
 def sha(b) -> str:
@@ -522,8 +544,15 @@ def main() -> int:
     total_bytes = cp.sum(step_bytes) * args.steps
     value = total_bytes / elapsed / GiB
 
+    # ---- the last timed step's output, before anything else writes the ring --------------
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(torch, args.dump_outputs, rank, world,
+                              {f"host_buffer_{i}": (b, cfg.get("chunk") or cfg["size"])
+                               for i, (b, _) in enumerate(hbufs)} if kind == "host" else {"ring": ring})
+
     single_call = None
-    if kind == "single":   # the same calls from a Python loop (ctypes), once, for comparison
+    if kind == "single" and args.full:   # the same calls from a Python loop (ctypes), once, for comparison
         single_step_py()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
@@ -634,6 +663,8 @@ def main() -> int:
         }
         if single_call:
             out["single_call"] = single_call
+        if dumped:
+            out["dumped_outputs"] = dumped
         print(json.dumps(out), flush=True)
     cp.close()
     return 0
@@ -647,6 +678,44 @@ def even_ring(n: int, cap_objs: int) -> int:
     cap_objs = max(1, min(n, cap_objs))
     passes = -(-n // cap_objs)
     return -(-n // passes)
+
+
+DUMP_BLOCK = 4096
+DUMP_BUDGET = 48 * MiB    # bytes of float32 written by --dump-outputs, over all ranks and arrays
+
+
+def dump_blocks(n_blocks: int, budget: int, seed: int = 0xD0) -> list[int]:
+    """The 4 KiB blocks --dump-outputs keeps of an n_blocks output within
+    `budget` bytes of float32: all of them when they fit, else the first, the
+    last and a seeded choice of the others (the same blocks on every run)."""
+    import random
+    keep = max(2, budget // (4 * DUMP_BLOCK))
+    if n_blocks <= keep:
+        return list(range(n_blocks))
+    return sorted({0, n_blocks - 1} | set(random.Random(seed).sample(range(1, n_blocks - 1), keep - 2)))
+
+
+def dump_outputs(torch, out_dir: str, rank: int, world: int, arrays: dict) -> dict:
+    """Write each output (a uint8 device tensor, or an (address, bytes) host
+    buffer) as <name>.npy (<name>_rank<r>.npy when N>1): float32, one row per
+    kept 4 KiB block (dump_blocks); bytes past the last whole block are not
+    written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BUDGET // world // max(1, len(arrays))
+    files = {}
+    for name, a in arrays.items():
+        if isinstance(a, tuple):
+            a = torch.from_numpy(np.ctypeslib.as_array((ctypes.c_uint8 * a[1]).from_address(a[0])))
+        nb = a.numel() // DUMP_BLOCK
+        idx = dump_blocks(nb, budget)
+        rows = a[:nb * DUMP_BLOCK].view(nb, DUMP_BLOCK)
+        if len(idx) < nb:
+            rows = torch.index_select(rows, 0, torch.tensor(idx, dtype=torch.int64, device=a.device))
+        fname = f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"
+        np.save(os.path.join(out_dir, fname), rows.cpu().numpy().astype(np.float32))
+        files[fname] = {"blocks": len(idx), "of": nb}
+    return {"dir": out_dir, "block_bytes": DUMP_BLOCK, "files": files}
 
 
 def launch_distribution(ms: list, nbytes: list, per_step: int = 1) -> dict:

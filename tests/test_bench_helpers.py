@@ -37,6 +37,45 @@ def test_launch_distribution_per_byte():
     assert d2["slow_launch_indices"] == [19] and d2["slow_by_position_in_step"][9] == 1
 
 
+def test_dump_blocks_fixed_choice_within_budget():
+    """--dump-outputs keeps every block of a small output, and of a large one
+    the first, the last and the same seeded choice on every call."""
+    assert bench.dump_blocks(0, bench.DUMP_BUDGET) == []
+    assert bench.dump_blocks(1000, bench.DUMP_BUDGET) == list(range(1000))
+    keep = bench.DUMP_BUDGET // (4 * bench.DUMP_BLOCK)
+    assert bench.dump_blocks(keep, bench.DUMP_BUDGET) == list(range(keep))
+    n = (80 << 30) // bench.DUMP_BLOCK                       # config 2's ring
+    idx = bench.dump_blocks(n, bench.DUMP_BUDGET)
+    assert idx == bench.dump_blocks(n, bench.DUMP_BUDGET)
+    assert len(idx) == keep == len(set(idx)) and idx == sorted(idx)
+    assert idx[0] == 0 and idx[-1] == n - 1
+    assert len(idx) * bench.DUMP_BLOCK * 4 <= 64 * 10**6     # float32 bytes written
+    assert len(bench.dump_blocks(n, bench.DUMP_BUDGET // 8)) == keep // 8
+
+
+def test_dump_outputs_host_buffer(tmp_path):
+    """A host buffer is written as float32 rows of 4 KiB blocks, whole blocks only."""
+    import numpy as np
+    import torch
+    a = (np.arange(3 * 4096 + 5) % 251).astype(np.uint8)
+    d = bench.dump_outputs(torch, str(tmp_path / "o"), 0, 1, {"host_buffer_0": (int(a.ctypes.data), a.size)})
+    got = np.load(tmp_path / "o" / "host_buffer_0.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 4096)
+    assert np.array_equal(got.astype(np.uint8).ravel(), a[:3 * 4096])
+    assert d["files"] == {"host_buffer_0.npy": {"blocks": 3, "of": 3}}
+
+
+def test_plain_run_switches_off_what_full_adds(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.steps == 3 and not a.full and a.dump_outputs is None
+    assert a.no_verify and a.no_ceiling and a.no_d2h and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-d2h", "--dump-outputs", "x"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "x" and a.no_d2h
+    assert not (a.no_verify or a.no_ceiling or a.no_cpu_baseline)
+
+
 def test_pin_cpus_within_affinity_one_per_core():
     aff = sorted(os.sched_getaffinity(0))
     n = min(4, len(aff))

@@ -22,7 +22,7 @@ def _run(args, timeout=240):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device-override", "0",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-ceiling"] + args
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-ceiling"] + args
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -9,7 +9,7 @@
 #   tests[:EXPR]        pytest -m gpu (optionally -k EXPR), log gpu_tests.log
 #   file:PATH           pytest -m gpu on one test file
 #   smoke               __graft_entry__.smoke()
-#   bench:CFG[:ARGS]    bench.py --config CFG --steps 20 --warmup 5 ARGS (':'-separated)
+#   bench:CFG[:ARGS]    bench.py --full --config CFG --steps 20 --warmup 5 ARGS (':'-separated)
 #   envbench:ENV:CFG    the same with ENV (comma-separated K=V) set
 #   driver              bench.py --gpus 1 --steps 20 --warmup 5 (the driver's own command; rounds 2-5 ran bench.py with no flags here, 5 steps)
 #   prof:CFG            rocprofv3 --kernel-trace --stats of bench.py --config CFG
@@ -46,12 +46,12 @@ for step in "$@"; do
         tail -2 "$OUT/$tag.log";;
     bench)
         extra=$(echo "${b}${c:+:$c}" | tr ':' ' ')
-        timeout -k 10 400 python -u bench.py --config "$a" --steps "$STEPS" --warmup "$WARMUP" $extra \
+        timeout -k 10 400 python -u bench.py --full --config "$a" --steps "$STEPS" --warmup "$WARMUP" $extra \
             > "$OUT/$tag.log" 2>&1; rc=$?
         grep '^{' "$OUT/$tag.log" | tail -1 | cut -c1-600;;
     envbench)
         envs=$(echo "$a" | tr ',' ' ')
-        timeout -k 10 400 env $envs python -u bench.py --config "$b" --steps "$STEPS" --warmup "$WARMUP" \
+        timeout -k 10 400 env $envs python -u bench.py --full --config "$b" --steps "$STEPS" --warmup "$WARMUP" \
             > "$OUT/$tag.log" 2>&1; rc=$?
         grep '^{' "$OUT/$tag.log" | tail -1 | cut -c1-600;;
     driver)
@@ -59,7 +59,7 @@ for step in "$@"; do
         grep '^{' "$OUT/$tag.log" | tail -1 | cut -c1-600;;
     prof)
         timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/$tag" -o run --output-format csv \
-            -- python3 bench.py --config "$a" --steps "$STEPS" --warmup "$WARMUP" --no-ceiling --no-d2h \
+            -- python3 bench.py --full --config "$a" --steps "$STEPS" --warmup "$WARMUP" --no-ceiling --no-d2h \
             --no-cpu-baseline > "$OUT/$tag.log" 2>&1; rc=$?
         grep '^{' "$OUT/$tag.log" | tail -1 | cut -c1-300;;
     pmc)
@@ -79,9 +79,9 @@ for step in "$@"; do
         timeout -k 10 300 "$a" > "$OUT/$tag.log" 2>&1; rc=$?
         tail -12 "$OUT/$tag.log";;
     rehearsal)      # N=8 / N=4 launcher rehearsals, every rank on device 0 (not a scaling measurement)
-        timeout -k 10 300 python bench.py --gpus 8 --device-override 0 --objects 64 --config 2 --steps 3 \
+        timeout -k 10 300 python bench.py --full --gpus 8 --device-override 0 --objects 64 --config 2 --steps 3 \
             --warmup 1 --no-ceiling > "$OUT/${tag}_n8_cfg2.log" 2>&1 && \
-        timeout -k 10 300 python bench.py --gpus 4 --device-override 0 --objects 400 --config 5 --steps 2 \
+        timeout -k 10 300 python bench.py --full --gpus 4 --device-override 0 --objects 400 --config 5 --steps 2 \
             --warmup 1 --d2h-full --no-ceiling > "$OUT/${tag}_n4_cfg5_d2h_full.log" 2>&1; rc=$?
         cat "$OUT/${tag}"_n*.log > "$OUT/$tag.log"
         grep -h '^{' "$OUT/${tag}"_n*.log | cut -c1-300;;

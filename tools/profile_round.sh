@@ -11,7 +11,7 @@ CFGS=${*:-2 3 4 5 6}
 mkdir -p $OUT
 for c in $CFGS; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace_cfg$c -o run --output-format csv -- \
-      python3 bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline --no-d2h > $OUT/bench_trace_cfg$c.log 2>&1 || { tail $OUT/bench_trace_cfg$c.log; exit 1; }
+      python3 bench.py --full --config $c --steps 20 --warmup 5 --no-cpu-baseline --no-d2h > $OUT/bench_trace_cfg$c.log 2>&1 || { tail $OUT/bench_trace_cfg$c.log; exit 1; }
   for ctr in WRITE_SIZE FETCH_SIZE; do
     timeout -s KILL 150 rocprofv3 --pmc $ctr -d $OUT/pmc_${ctr}_cfg$c -o run --output-format csv -- \
         python3 bench.py --config $c --steps 1 --warmup 0 --no-cpu-baseline --no-d2h --no-verify --no-ceiling > $OUT/bench_pmc_${ctr}_cfg$c.log 2>&1 || { tail $OUT/bench_pmc_${ctr}_cfg$c.log; exit 1; }
