@@ -260,6 +260,36 @@ int s3dg_write_ceiling_tiled(s3dg_ctx *ctx, void *dst, uint64_t len, uint32_t pa
  * len < 8 MiB or a multiple of 8 MiB. */
 int s3dg_write_ceiling_fill(s3dg_ctx *ctx, void *dst, uint64_t len, uint32_t pace, void *stream);
 
+/* ---- device-resident verification (synchronous on `stream`) -------------- */
+/* The read-side twins of the s3dg_fill_* calls above (4 KiB-block layouts):
+ * the GPU recomputes every block from (size, dedup, f_num/f_den, entropy, base
+ * block) and compares it with the bytes at `src`; nothing is written to `src`,
+ * and no byte at or past an object's end (stride gaps included) is read.
+ * Arguments, alignment rules (16-byte `src` and `stride`) and S3DG_EINVAL
+ * cases are those of the matching fill call; a null `out` is S3DG_EINVAL.
+ * Each call enqueues on `stream`, waits for it and fills *out; a zero-length
+ * call launches nothing and returns {0, 0, UINT64_MAX}.  Calls on different
+ * streams of one context share no state. */
+typedef struct {
+    uint64_t mismatched_bytes;   /* bytes that differ from the expected payload */
+    uint64_t mismatched_blocks;  /* 4 KiB blocks (per object) holding at least one */
+    uint64_t first_offset;       /* lowest differing byte offset from `src`
+                                    (stride gaps included); UINT64_MAX = none */
+} s3dg_verify_result;
+int s3dg_verify_controlled(s3dg_ctx *ctx, const void *src, uint64_t len, uint64_t dedup,
+                           uint32_t f_num, uint32_t f_den, uint64_t entropy, void *stream,
+                           s3dg_verify_result *out);
+/* Blocks [blk_lo, blk_hi) of one `len`-byte object, block blk_lo at src. */
+int s3dg_verify_controlled_range(s3dg_ctx *ctx, const void *src, uint64_t len, uint64_t blk_lo,
+                                 uint64_t blk_hi, uint64_t dedup, uint32_t f_num, uint32_t f_den,
+                                 uint64_t entropy, void *stream, s3dg_verify_result *out);
+int s3dg_verify_random_data(s3dg_ctx *ctx, const void *src, uint64_t len, uint64_t entropy,
+                            void *stream, s3dg_verify_result *out);
+int s3dg_verify_controlled_stream(s3dg_ctx *ctx, const void *src, uint64_t obj_size, uint64_t stride,
+                                  uint64_t n_objs, uint64_t dedup, uint32_t f_num, uint32_t f_den,
+                                  uint64_t seed_base, uint64_t first_obj, void *stream,
+                                  s3dg_verify_result *out);
+
 /* ---- memory / copy helpers ------------------------------------------------ */
 int s3dg_device_alloc(s3dg_ctx *ctx, uint64_t bytes, void **out);
 int s3dg_device_free(s3dg_ctx *ctx, void *p);
@@ -451,6 +481,13 @@ int s3dlio_fill_controlled_data(uint8_t *buf, size_t len, size_t dedup, size_t c
 int s3dlio_fill_controlled_data_seeded(uint8_t *buf, size_t len, size_t dedup,
                                        size_t compress, uint64_t entropy,
                                        const uint8_t *base4096);
+/* Its read-side twin: compare buf[0, len) with what the seeded fill would
+ * write for (dedup, compress, entropy, base4096), on a host slot's GPU.  Any
+ * alignment, read-only memory included; nothing is written to buf.  Empty
+ * buffer: {0, 0, UINT64_MAX} without touching the GPU. */
+int s3dlio_verify_controlled_data_seeded(const uint8_t *buf, size_t len, size_t dedup,
+                                         size_t compress, uint64_t entropy,
+                                         const uint8_t *base4096, s3dg_verify_result *out);
 
 const char *s3dg_last_error(void);
 const char *s3dg_version(void);

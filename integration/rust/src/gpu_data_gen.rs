@@ -41,6 +41,31 @@ struct S3dgGen {
     _p: [u8; 0],
 }
 
+/// `s3dg_verify_result` (include/s3dlio_gpu.h): what a verify call found.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct VerifyResult {
+    /// bytes that differ from the expected payload
+    pub mismatched_bytes: u64,
+    /// 4 KiB blocks holding at least one
+    pub mismatched_blocks: u64,
+    /// lowest differing byte offset; `u64::MAX` = none
+    pub first_offset: u64,
+}
+
+impl VerifyResult {
+    pub const CLEAN: VerifyResult = VerifyResult { mismatched_bytes: 0, mismatched_blocks: 0, first_offset: u64::MAX };
+
+    pub fn is_ok(&self) -> bool {
+        self.mismatched_bytes == 0
+    }
+
+    /// The lowest differing byte offset, if any.
+    pub fn first(&self) -> Option<u64> {
+        if self.first_offset == u64::MAX { None } else { Some(self.first_offset) }
+    }
+}
+
 // include/s3dlio_gpu.h constants
 const S3DG_OBJ_NPZ: c_int = 0;
 const S3DG_OBJ_TFRECORD: c_int = 1;
@@ -54,6 +79,9 @@ extern "C" {
     fn s3dlio_fill_controlled_data(buf: *mut u8, len: usize, dedup: usize, compress: usize) -> c_int;
     fn s3dlio_fill_controlled_data_seeded(buf: *mut u8, len: usize, dedup: usize, compress: usize,
                                           entropy: u64, base4096: *const u8) -> c_int;
+    fn s3dlio_verify_controlled_data_seeded(buf: *const u8, len: usize, dedup: usize, compress: usize,
+                                            entropy: u64, base4096: *const u8,
+                                            out: *mut VerifyResult) -> c_int;
     fn s3dlio_generate_random_data(buf: *mut u8, size: usize) -> c_int;
     fn s3dg_object_size(object_type: c_int, elements: u64, element_size: u64, out: *mut u64) -> c_int;
     fn s3dg_generate_object(object_type: c_int, elements: u64, element_size: u64, use_controlled: c_int,
@@ -115,6 +143,22 @@ pub fn fill_controlled_data_seeded(buf: &mut [u8], dedup: usize, compress: usize
     }
     let p = base.map_or(std::ptr::null(), |b| b.as_ptr());
     check(unsafe { s3dlio_fill_controlled_data_seeded(buf.as_mut_ptr(), buf.len(), dedup, compress, entropy, p) })
+}
+
+/// Read-side twin of `fill_controlled_data_seeded`: compares `buf` on the GPU
+/// with the bytes that call would write for the same arguments (any
+/// alignment; nothing is written).  An empty buffer is clean without a GPU.
+pub fn verify_controlled_data_seeded(buf: &[u8], dedup: usize, compress: usize, entropy: u64,
+                                     base: Option<&[u8; 4096]>) -> anyhow::Result<VerifyResult> {
+    let mut out = VerifyResult::CLEAN;
+    if buf.is_empty() {
+        return Ok(out);
+    }
+    let p = base.map_or(std::ptr::null(), |b| b.as_ptr());
+    check(unsafe {
+        s3dlio_verify_controlled_data_seeded(buf.as_ptr(), buf.len(), dedup, compress, entropy, p, &mut out)
+    })?;
+    Ok(out)
 }
 
 /// A reused caller buffer page-locked for direct kernel stores

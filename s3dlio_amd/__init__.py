@@ -7,11 +7,11 @@ the library is absent (no CPU fallback exists).
 """
 from ._lib import S3dgError, lib  # noqa: F401  (loads libs3dlio_amd.so)
 from .hostbuf import BytesView  # noqa: F401
-from .device import (BLOCK_SIZE, DEFAULT_BASE_SEED, Context, compress_ratio,  # noqa: F401
+from .device import (BLOCK_SIZE, DEFAULT_BASE_SEED, Context, VerifyResult, compress_ratio,  # noqa: F401
                      device_count, host_context, host_slots, object_entropy, parse_devices,
                      unique_blocks, xoshiro_jump)
 from .data_gen import (HostRegistration, fill_controlled_data, fill_controlled_data_seeded,  # noqa: F401
-                       register_host_buffer, unregister_host_buffer)
+                       register_host_buffer, unregister_host_buffer, verify_controlled_data_seeded)
 from .datagen import (DataGenerator, Generator, ObjectGen, default_data_gen_threads,  # noqa: F401
                       generate_controlled_data_alt, generate_controlled_data_streaming,
                       generate_data, generate_data_with_threads, generate_into_buffer,
@@ -25,7 +25,7 @@ from .objects import (Config, DataGenMode, ObjectType, build_npz, build_raw,  # 
                       build_tfrecord, build_tfrecord_with_index, generate_object,
                       generate_random_data, object_size)
 
-from .put import (DEFAULT_OBJECT_SIZE, PutResult, build_uri_list, put,  # noqa: F401
-                  put_objects, put_objects_with_random_data_and_type)
+from .put import (DEFAULT_OBJECT_SIZE, PutResult, VerifyObjectsResult, build_uri_list, put,  # noqa: F401
+                  put_objects, put_objects_with_random_data_and_type, verify_objects)
 
 __version__ = "0.1.0"

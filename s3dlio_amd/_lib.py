@@ -48,6 +48,11 @@ class PutStats(ctypes.Structure):
                 ("gpu_seconds", ctypes.c_double)]
 
 
+class VerifyRec(ctypes.Structure):
+    """s3dg_verify_result"""
+    _fields_ = [("mismatched_bytes", c_u64), ("mismatched_blocks", c_u64), ("first_offset", c_u64)]
+
+
 # name -> (restype, argtypes); the exact export list of include/s3dlio_gpu.h
 SIGNATURES = {
     "s3dg_ctx_create": (c_int, [c_int, ctypes.POINTER(c_vp)]),
@@ -85,6 +90,13 @@ SIGNATURES = {
     "s3dg_fill_controlled_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_u64, c_u32, c_u32,
                                             c_u64, c_u64, c_vp]),
     "s3dg_fill_controlled_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(ObjDesc), c_u64, c_vp]),
+    "s3dg_verify_controlled": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u32, c_u32, c_u64, c_vp,
+                                       ctypes.POINTER(VerifyRec)]),
+    "s3dg_verify_controlled_range": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_u64, c_u32, c_u32,
+                                             c_u64, c_vp, ctypes.POINTER(VerifyRec)]),
+    "s3dg_verify_random_data": (c_int, [c_vp, c_vp, c_u64, c_u64, c_vp, ctypes.POINTER(VerifyRec)]),
+    "s3dg_verify_controlled_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_u64, c_u32, c_u32,
+                                              c_u64, c_u64, c_vp, ctypes.POINTER(VerifyRec)]),
     "s3dg_write_ceiling": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
     "s3dg_write_ceiling_tiled": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
     "s3dg_write_ceiling_fill": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
@@ -139,6 +151,9 @@ SIGNATURES = {
                                             ctypes.c_size_t]),
     "s3dlio_fill_controlled_data_seeded": (c_int, [c_vp, ctypes.c_size_t, ctypes.c_size_t,
                                                    ctypes.c_size_t, c_u64, c_u8p]),
+    "s3dlio_verify_controlled_data_seeded": (c_int, [c_vp, ctypes.c_size_t, ctypes.c_size_t,
+                                                     ctypes.c_size_t, c_u64, c_u8p,
+                                                     ctypes.POINTER(VerifyRec)]),
     "s3dg_object_size": (c_int, [c_int, c_u64, c_u64, ctypes.POINTER(c_u64)]),
     "s3dg_generate_object": (c_int, [c_int, c_u64, c_u64, c_int, c_u64, c_u64, c_int, c_int, c_u64,
                                      c_vp, c_u64, ctypes.POINTER(c_u64)]),

@@ -250,6 +250,7 @@ struct s3dg_ctx {
     uint32_t *crc_seg = nullptr;       // per-segment CRCs (device)
     uint64_t crc_seg_cap = 0;
     std::mutex crc_mu;
+    std::vector<VerifyRec *> vrecs;    // idle verify result records (device; under mu), one taken per call
     ZcTuner tune[3];                   // per zero class (under mu)
     std::mutex mu;
 };
@@ -587,6 +588,7 @@ int s3dg_ctx_destroy(s3dg_ctx *c) {
     for (auto &kv : c->jtabs) (void)hipFree(kv.second);
     if (c->crc_tab) (void)hipFree(c->crc_tab);
     if (c->crc_seg) (void)hipFree(c->crc_seg);
+    for (VerifyRec *r : c->vrecs) (void)hipFree(r);
     for (auto &T : c->tune) {
         for (auto &p : T.pend) {
             (void)hipEventDestroy(p.a);
@@ -1003,6 +1005,106 @@ int s3dg_fill_controlled_stream(s3dg_ctx *c, void *dst, uint64_t obj_size, uint6
     PrefixParams pp;
     if (int r = make_prefix(nb, dedup, f_num, f_den, &pp)) return r;
     return fill_uniform(c, (uint8_t *)dst, obj_size, stride, n_objs, pp, seed_base, first_obj, (hipStream_t)stream);
+}
+
+// ---- verification (k_verify_stream) -------------------------------------------
+// One call: a result record of its own (from the context's idle list, so two
+// threads on two streams never share one), reset on the stream, the launch,
+// the record copied back, the stream drained.
+static int verify_run(s3dg_ctx *c, const void *src, uint64_t obj_size, uint64_t stride, uint64_t n_objs,
+                      uint64_t blk_lo, uint64_t blk_hi, uint64_t seed_base, uint64_t first_obj,
+                      const PrefixParams &pp, hipStream_t s, s3dg_verify_result *out) {
+    VerifyRec *rec = nullptr;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (!c->vrecs.empty()) {
+            rec = c->vrecs.back();
+            c->vrecs.pop_back();
+        }
+    }
+    if (!rec) HIP_TRY(hipMalloc((void **)&rec, sizeof(VerifyRec)), "hipMalloc(verify record)");
+    VerifyRec host{0, 0, UINT64_MAX};
+    hipError_t e = verify_rec_reset(rec, s);
+    const char *what = "hipMemsetAsync(verify record)";
+    if (e == hipSuccess) {
+        e = launch_verify_stream(cfg_for(c), (const uint8_t *)src, obj_size, stride, n_objs, (uint32_t)blk_lo,
+                                 (uint32_t)blk_hi, seed_base, first_obj, pp, c->base_dev, 0, rec, s);
+        what = "launch k_verify_stream";
+    }
+    if (e == hipSuccess) {
+        e = hipMemcpyAsync(&host, rec, sizeof(host), hipMemcpyDeviceToHost, s);
+        what = "hipMemcpyAsync(verify record)";
+    }
+    // drained on every path: the record goes back to the list only when idle
+    const hipError_t se = hipStreamSynchronize(s);
+    if (e == hipSuccess && se != hipSuccess) {
+        e = se;
+        what = "hipStreamSynchronize(verify)";
+    }
+    if (se == hipSuccess) {
+        std::lock_guard<std::mutex> g(c->mu);
+        c->vrecs.push_back(rec);
+    }
+    HIP_TRY(e, what);
+    out->mismatched_bytes = host.bytes;
+    out->mismatched_blocks = host.blocks;
+    out->first_offset = host.first;
+    return S3DG_OK;
+}
+
+static void verify_clean(s3dg_verify_result *out) {
+    out->mismatched_bytes = 0;
+    out->mismatched_blocks = 0;
+    out->first_offset = UINT64_MAX;
+}
+
+int s3dg_verify_controlled_range(s3dg_ctx *c, const void *src, uint64_t len, uint64_t blk_lo, uint64_t blk_hi,
+                                 uint64_t dedup, uint32_t f_num, uint32_t f_den, uint64_t entropy, void *stream,
+                                 s3dg_verify_result *out) {
+    CTX_SCOPE(c);
+    if (!out) return fail(S3DG_EINVAL, "null output");
+    verify_clean(out);
+    if (len == 0) return S3DG_OK;
+    const uint64_t nb = (len + kBlk - 1) / kBlk;
+    if (blk_hi > nb) blk_hi = nb;
+    if (blk_lo >= blk_hi) return S3DG_OK;
+    if (!src || !aligned16(src)) return fail(S3DG_EINVAL, "src must be a 16-byte aligned device pointer");
+    PrefixParams pp;
+    if (int r = make_prefix(nb, dedup, f_num, f_den, &pp)) return r;
+    return verify_run(c, src, len, 0, 1, blk_lo, blk_hi, entropy, 0, pp, (hipStream_t)stream, out);
+}
+
+int s3dg_verify_controlled(s3dg_ctx *c, const void *src, uint64_t len, uint64_t dedup, uint32_t f_num,
+                           uint32_t f_den, uint64_t entropy, void *stream, s3dg_verify_result *out) {
+    return s3dg_verify_controlled_range(c, src, len, 0, ~0ull, dedup, f_num, f_den, entropy, stream, out);
+}
+
+int s3dg_verify_random_data(s3dg_ctx *c, const void *src, uint64_t len, uint64_t entropy, void *stream,
+                            s3dg_verify_result *out) {
+    CTX_SCOPE(c);
+    if (!out) return fail(S3DG_EINVAL, "null output");
+    verify_clean(out);
+    if (len == 0) return S3DG_OK;
+    if (!src || !aligned16(src)) return fail(S3DG_EINVAL, "src must be a 16-byte aligned device pointer");
+    const uint64_t nb = (len + kBlk - 1) / kBlk;
+    if (nb > 0xFFFFFFFFull) return fail(S3DG_EINVAL, "object larger than 2^32 blocks");
+    return verify_run(c, src, len, 0, 1, 0, nb, entropy, 0, random_layout_prefix(), (hipStream_t)stream, out);
+}
+
+int s3dg_verify_controlled_stream(s3dg_ctx *c, const void *src, uint64_t obj_size, uint64_t stride,
+                                  uint64_t n_objs, uint64_t dedup, uint32_t f_num, uint32_t f_den,
+                                  uint64_t seed_base, uint64_t first_obj, void *stream, s3dg_verify_result *out) {
+    CTX_SCOPE(c);
+    if (!out) return fail(S3DG_EINVAL, "null output");
+    verify_clean(out);
+    if (obj_size == 0 || n_objs == 0) return S3DG_OK;
+    if (!src || !aligned16(src) || (stride & 15u))
+        return fail(S3DG_EINVAL, "src and stride must be 16-byte aligned");
+    if (n_objs > 1 && stride < obj_size) return fail(S3DG_EINVAL, "stride < obj_size: objects overlap");
+    const uint64_t nb = (obj_size + kBlk - 1) / kBlk;
+    PrefixParams pp;
+    if (int r = make_prefix(nb, dedup, f_num, f_den, &pp)) return r;
+    return verify_run(c, src, obj_size, stride, n_objs, 0, nb, seed_base, first_obj, pp, (hipStream_t)stream, out);
 }
 
 int s3dg_set_stream_tiles(s3dg_ctx *c, int on) {

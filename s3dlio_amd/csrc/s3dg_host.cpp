@@ -192,6 +192,7 @@ void staging_free(HostStaging *sg) {
     for (auto &e : sg->ev)
         if (e) (void)hipEventDestroy(e);
     if (sg->base_user) (void)hipFree(sg->base_user);
+    if (sg->vrec) (void)hipFree(sg->vrec);
     delete sg;
 }
 
@@ -752,6 +753,51 @@ int host_run_split(HostStaging *sg0, const HostJob &J, uint8_t *buf, uint64_t po
     return rc[0];
 }
 
+// Verify buf[0, n) (any alignment, read-only memory included) against the
+// job's object: 64 MiB chunks copied H2D into the staging set's two device
+// chunks on its two streams in turn (chunk k+1's copy overlaps chunk k's
+// kernel), each verified as a block range of the object.  The chunks add into
+// one device record of the staging set, each launch offset by its chunk's
+// position in buf, so the record read back at the end holds the call's sums
+// and its lowest differing offset.
+static int host_verify(HostStaging *sg, const HostJob &J, const uint8_t *buf, uint64_t n, s3dg_verify_result *out) {
+    Slot *S = pool().slots[sg->slot];
+    DeviceScope ds(S->device);
+    H_TRY(ds.err, "hipSetDevice");
+    auto run = [&]() -> int {
+        if (int r = upload_user_base(sg, J)) return r;
+        const void *base = base_for(S, sg, J);
+        if (!sg->vrec) H_TRY(hipMalloc((void **)&sg->vrec, sizeof(VerifyRec)), "hipMalloc(verify record)");
+        H_TRY(verify_rec_reset(sg->vrec, sg->st[0]), "hipMemsetAsync(verify record)");
+        H_TRY(hipStreamSynchronize(sg->st[0]), "hipStreamSynchronize");   // before the other stream adds to it
+        const uint64_t per = kChunk / kBlk, nb = (n + kBlk - 1) / kBlk;
+        int k = 0;
+        for (uint64_t pb = 0; pb < nb; pb += per, ++k) {
+            const uint64_t pe = pb + per < nb ? pb + per : nb;
+            const int sl = k & 1;
+            const uint64_t lo = pb * kBlk, hi = pe * kBlk < n ? pe * kBlk : n;
+            H_TRY(hipMemcpyAsync(sg->buf[sl], buf + lo, hi - lo, hipMemcpyHostToDevice, sg->st[sl]),
+                  "hipMemcpyAsync(H2D)");
+            H_TRY(launch_verify_stream(ctx_stream_cfg(S->ctx), (const uint8_t *)sg->buf[sl], J.obj_len, 0, 1,
+                                       (uint32_t)pb, (uint32_t)pe, J.entropy, 0, J.pp, base, lo, sg->vrec,
+                                       sg->st[sl]),
+                  "launch k_verify_stream(host chunk)");
+        }
+        H_TRY(hipStreamSynchronize(sg->st[0]), "hipStreamSynchronize");
+        H_TRY(hipStreamSynchronize(sg->st[1]), "hipStreamSynchronize");
+        VerifyRec host{};
+        H_TRY(hipMemcpy(&host, sg->vrec, sizeof(host), hipMemcpyDeviceToHost), "hipMemcpy(verify record)");
+        out->mismatched_bytes = host.bytes;
+        out->mismatched_blocks = host.blocks;
+        out->first_offset = host.first;
+        return S3DG_OK;
+    };
+    const int r = run();
+    if (r != S3DG_OK)
+        for (int q = 0; q < 2; ++q) (void)hipStreamSynchronize(sg->st[q]);   // no copy still reads buf
+    return r;
+}
+
 // One-shot: a slot round-robin, a staging set for the call, split over slots.
 static int host_oneshot(const HostJob &J, uint8_t *buf, uint64_t len) {
     int slot = 0;
@@ -898,6 +944,28 @@ int s3dlio_fill_controlled_data_seeded(uint8_t *buf, size_t len, size_t dedup, s
     J.base = base4096 ? HostJob::kBaseUser : HostJob::kBaseCtx;
     J.user_base = base4096;
     return host_oneshot(J, buf, len);
+}
+
+int s3dlio_verify_controlled_data_seeded(const uint8_t *buf, size_t len, size_t dedup, size_t compress,
+                                         uint64_t entropy, const uint8_t *base4096, s3dg_verify_result *out) {
+    if (!out) return s3dg_internal_fail(S3DG_EINVAL, "null output");
+    out->mismatched_bytes = 0;
+    out->mismatched_blocks = 0;
+    out->first_offset = UINT64_MAX;
+    if (len == 0) return S3DG_OK;
+    if (!buf) return s3dg_internal_fail(S3DG_EINVAL, "null buffer");
+    HostJob J;
+    if (int r = controlled_job(J, len, dedup, compress)) return r;
+    J.entropy = entropy;
+    J.base = base4096 ? HostJob::kBaseUser : HostJob::kBaseCtx;
+    J.user_base = base4096;
+    int slot = 0;
+    if (int r = host_next_slot(&slot)) return r;
+    HostStaging *sg = nullptr;
+    if (int r = host_staging_acquire(slot, &sg)) return r;
+    const int r = host_verify(sg, J, buf, len, out);
+    host_staging_release(sg);
+    return r;
 }
 
 }  // extern "C"

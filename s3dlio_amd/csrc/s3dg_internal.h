@@ -86,6 +86,20 @@ hipError_t launch_fill_stream(const LaunchCfg &lc, uint8_t *dst, uint64_t obj_si
                               uint32_t blk_hi, uint64_t seed_base, uint64_t first_obj,
                               PrefixParams pp, const void *base_dev, hipStream_t s);
 
+// Verify (k_verify_stream): the layout of s3dg_verify_result, accumulated on
+// the device.  The caller owns `rec` for the call and zeroes it (first =
+// UINT64_MAX) on the stream before the launch; off0 is added to every
+// reported offset.
+struct VerifyRec {
+    uint64_t bytes, blocks, first;
+};
+static_assert(sizeof(VerifyRec) == sizeof(s3dg_verify_result), "VerifyRec is s3dg_verify_result");
+hipError_t launch_verify_stream(const LaunchCfg &lc, const uint8_t *src, uint64_t obj_size, uint64_t stride,
+                                uint64_t n_objs, uint32_t blk_lo, uint32_t blk_hi, uint64_t seed_base,
+                                uint64_t first_obj, PrefixParams pp, const void *base_dev, uint64_t off0,
+                                VerifyRec *rec, hipStream_t s);
+hipError_t verify_rec_reset(VerifyRec *rec, hipStream_t s);   // {0, 0, UINT64_MAX}, on the stream
+
 // Batch records built on the device from the uploaded descriptors (the scan,
 // then k_batch_map: prefix parameters per object and its records), then
 // k_fill_batch over total_recs << tshift slots.
@@ -228,6 +242,7 @@ struct HostStaging {
     uint8_t *bounce = nullptr;           // pinned, small calls (lazily)
     uint64_t bounce_bytes = 0;
     hipEvent_t ev[kSmallPieces] = {};
+    VerifyRec *vrec = nullptr;           // device result record of a verify call (lazily)
 };
 // What to generate into host memory: the fill_controlled_data / random-data
 // layouts (4 KiB blocks, pp) or DG1 (dgen = true, 1 MiB blocks).

@@ -365,6 +365,115 @@ __global__ __launch_bounds__(64 * NW) void k_fill_stream(uint8_t *dst, const u32
                       ent0 + ((uint64_t)blockIdx.y << 32), pp, B);
 }
 
+// Differing bytes of one 16-byte piece (x = loaded ^ expected, known to be
+// non-zero somewhere): their count, and the block offset of the lowest one.
+__device__ __forceinline__ void diff_piece(u32x4 x, uint32_t o, uint32_t &cnt, uint32_t &first) {
+    const uint32_t dw[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int q = 3; q >= 0; --q) {
+        uint32_t m = dw[q] | (dw[q] >> 4);   // bit 8b set <=> byte b of the dword differs
+        m |= m >> 2;
+        m |= m >> 1;
+        m &= 0x01010101u;
+        if (m) {
+            cnt += __builtin_popcount(m);
+            const uint32_t p = o + 4 * q + ((uint32_t)__builtin_ctz(m) >> 3);
+            first = p < first ? p : first;
+        }
+    }
+}
+
+// Verify, the read-side twin of k_fill_stream (same grid, same phases 1-2):
+// the workgroup rebuilds its block's LDS image exactly as the fill does, then
+// each thread compares its 16-byte pieces of `src` with the expected piece
+// (zero below c, else the image) instead of storing them.  The loads of the
+// whole pieces are issued first, beside the base block's, so HBM latency
+// overlaps the plan; a piece is whole when it ends at or below the block's
+// length L, and the ragged piece of an object's last block is read byte by
+// byte below L only (as write_block stores it): no byte at or past the
+// object's end is ever loaded.  Counts are reduced over the wave by shuffles
+// and over the waves through LDS; thread 0 touches the result record (two
+// 64-bit adds and a 64-bit min, vector atomics) only when the block's count is
+// non-zero, so a clean block costs no store and no atomic.  off0: byte offset
+// of this launch's src from the caller's (sub-launches, host chunks).
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void k_verify_stream(const uint8_t *src, const u32x4 *base, uint64_t stride,
+                                                           uint64_t ent0, uint64_t obj_size, uint32_t blk_lo,
+                                                           PrefixParams pp, uint64_t off0, VerifyRec *rec) {
+    constexpr int T = 64 * NW, SPL = 4 / NW;
+    __shared__ __attribute__((aligned(16))) BlockLds S;
+    __shared__ uint32_t wcnt[NW], wfirst[NW];
+    const uint32_t t = threadIdx.x;
+    const uint32_t lane = t & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const uint32_t i = blk_lo + blockIdx.x;
+    const uint64_t boff = (uint64_t)blockIdx.y * stride + (uint64_t)blockIdx.x * kBlk;
+    const uint8_t *bs = src + boff;
+    const uint64_t left = obj_size - (uint64_t)i * kBlk;          // the launcher keeps i * 4 KiB < obj_size
+    const uint32_t L = left < kBlk ? (uint32_t)left : kBlk;       // = Plan::L
+    u32x4 B[SPL], G[SPL];
+    load_base<NW>(B, t, base);
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+        const uint32_t o = (t + k * T) * 16;
+        G[k] = u32x4{0u, 0u, 0u, 0u};
+        // nontemporal (global_load_dwordx4 ... nt): the bytes are read once; 1.3 % over
+        // plain loads in three alternating pairs on one box (profiles/verify/nt_ab.log)
+        if (o + 16 <= L) G[k] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(bs + o));
+    }
+    Plan P;
+    if (wave == 0) {
+        plan_block<false>(P, lane, i, obj_size, ent0 + ((uint64_t)blockIdx.y << 32), pp);
+        if (lane == 0) { S.meta[0] = P.c; S.meta[1] = P.L; }
+    }
+    store_image<NW>(S, t, B);
+    __syncthreads();
+    if (wave == 0) patch_image(S, P, lane);
+    __syncthreads();
+    const uint32_t c = S.meta[0];
+    uint32_t cnt = 0, first = kBlk;                               // kBlk: no differing byte
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+        const uint32_t o = (t + k * T) * 16;
+        if (o >= L) continue;
+        u32x4 e = {0u, 0u, 0u, 0u};
+        if (o + 16 > c) e = *reinterpret_cast<const u32x4 *>(S.img + o);
+        if (o + 16 <= L) {
+            const u32x4 x = G[k] ^ e;
+            if (x.x | x.y | x.z | x.w) diff_piece(x, o, cnt, first);
+        } else {                                                  // ragged object tail: bytes < L only
+            const uint32_t dw[4] = {e.x, e.y, e.z, e.w};
+            for (uint32_t b = 0; o + b < L; ++b)
+                if (bs[o + b] != (uint8_t)(dw[b >> 2] >> (8 * (b & 3)))) {
+                    ++cnt;
+                    first = o + b < first ? o + b : first;
+                }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        cnt += __shfl_xor(cnt, d, 64);
+        const uint32_t f = __shfl_xor(first, d, 64);
+        first = f < first ? f : first;
+    }
+    if constexpr (NW > 1) {
+        if (lane == 0) { wcnt[wave] = cnt; wfirst[wave] = first; }
+        __syncthreads();
+        if (t == 0) {
+#pragma unroll
+            for (int w = 1; w < NW; ++w) {
+                cnt += wcnt[w];
+                first = wfirst[w] < first ? wfirst[w] : first;
+            }
+        }
+    }
+    if (t == 0 && cnt) {
+        atomicAdd(reinterpret_cast<unsigned long long *>(&rec->bytes), (unsigned long long)cnt);
+        atomicAdd(reinterpret_cast<unsigned long long *>(&rec->blocks), 1ull);
+        atomicMin(reinterpret_cast<unsigned long long *>(&rec->first), (unsigned long long)(off0 + boff + first));
+    }
+}
+
 // Batch: workgroup g -> tile record g >> tshift (one scalar load), block
 // first + (g mod 2^tshift) - lead of that object; slots before the object's
 // start (lead) or past its end exit.  lead makes g = 4 KiB-granule address
@@ -1154,6 +1263,46 @@ hipError_t launch_fill_stream(const LaunchCfg &lc, uint8_t *dst, uint64_t obj_si
         }
     }
     return hipSuccess;
+}
+
+// The verify twin of launch_fill_stream: same y / x splits, each sub-launch
+// given its byte offset from `src` (plus off0) so the record's first offset is
+// relative to the caller's buffer.  rec (device) accumulates; the caller
+// zeroes it on the stream first.  No occupancy cap: the pass only reads.
+hipError_t launch_verify_stream(const LaunchCfg &lc, const uint8_t *src, uint64_t obj_size, uint64_t stride,
+                                uint64_t n_objs, uint32_t blk_lo, uint32_t blk_hi, uint64_t seed_base,
+                                uint64_t first_obj, PrefixParams pp, const void *base_dev, uint64_t off0,
+                                VerifyRec *rec, hipStream_t s) {
+    (void)hipGetLastError();
+    const u32x4 *b = reinterpret_cast<const u32x4 *>(base_dev);
+    const uint32_t nx = blk_hi - blk_lo;
+    for (uint64_t y0 = 0; y0 < n_objs; y0 += 65535) {
+        const uint32_t ny = (uint32_t)((n_objs - y0) < 65535 ? (n_objs - y0) : 65535);
+        for (uint64_t x0 = 0; x0 < nx; x0 += kMaxGridX) {
+            const uint32_t gx = (uint32_t)((nx - x0) < kMaxGridX ? (nx - x0) : kMaxGridX);
+            const uint64_t sub = y0 * stride + x0 * kBlk;
+            const uint64_t ent0 = seed_base + ((first_obj + y0) << 32);
+            const dim3 g(gx, ny);
+            if (lc.waves_per_block == 1)
+                hipLaunchKernelGGL((k_verify_stream<1>), g, dim3(64), 0, s, src + sub, b, stride, ent0, obj_size,
+                                   (uint32_t)(blk_lo + x0), pp, off0 + sub, rec);
+            else if (lc.waves_per_block == 4)
+                hipLaunchKernelGGL((k_verify_stream<4>), g, dim3(256), 0, s, src + sub, b, stride, ent0, obj_size,
+                                   (uint32_t)(blk_lo + x0), pp, off0 + sub, rec);
+            else
+                hipLaunchKernelGGL((k_verify_stream<2>), g, dim3(128), 0, s, src + sub, b, stride, ent0, obj_size,
+                                   (uint32_t)(blk_lo + x0), pp, off0 + sub, rec);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
+}
+
+hipError_t verify_rec_reset(VerifyRec *rec, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(rec, 0, 2 * sizeof(uint64_t), s);
+    if (e == hipSuccess) e = hipMemsetAsync(&rec->first, 0xFF, sizeof(uint64_t), s);
+    return e;
 }
 
 static hipError_t batch_tiles(const LaunchCfg &lc, uint8_t *dst_base, uint64_t total_tiles, uint32_t tshift,

@@ -12,6 +12,7 @@ the entropy and base block made explicit.
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass
 from fractions import Fraction
 
 import numpy as np
@@ -52,6 +53,23 @@ def unique_blocks(nblocks: int, dedup: int) -> int:
 
 def object_entropy(seed_base: int, j: int) -> int:
     return int(lib.s3dg_object_entropy(seed_base & (2**64 - 1), j))
+
+
+@dataclass(frozen=True)
+class VerifyResult:
+    """s3dg_verify_result: what a verify call found."""
+    mismatched_bytes: int = 0     # bytes that differ from the expected payload
+    mismatched_blocks: int = 0    # 4 KiB blocks (per object) holding at least one
+    first_offset: int | None = None   # lowest differing byte offset from the start; None = clean
+
+    @property
+    def ok(self) -> bool:
+        return self.mismatched_bytes == 0
+
+    @classmethod
+    def _of(cls, r) -> "VerifyResult":
+        first = int(r.first_offset)
+        return cls(int(r.mismatched_bytes), int(r.mismatched_blocks), None if first == 2**64 - 1 else first)
 
 
 def _ptr(x) -> int:
@@ -240,7 +258,7 @@ class Context:
     # every byte the call writes (ValueError otherwise: the C ABI only sees a
     # pointer and would write past the allocation).  A raw int pointer is the
     # caller's responsibility.
-    def _dst(self, x, need: int) -> int:
+    def _dst(self, x, need: int, verb: str = "writes") -> int:
         p = _ptr(x)
         if not isinstance(x, int):
             idx = x.device.index if x.device.index is not None else 0
@@ -248,7 +266,7 @@ class Context:
                 raise ValueError(f"tensor is on cuda:{idx}, this context is on cuda:{self.device}")
             have = _nbytes(x)
             if need > have:
-                raise ValueError(f"the call writes {need} bytes, the tensor holds {have}")
+                raise ValueError(f"the call {verb} {need} bytes, the tensor holds {have}")
         return p
 
     def _s(self, stream) -> int:
@@ -289,6 +307,58 @@ class Context:
         call("s3dg_fill_controlled_stream", self._h, self._dst(dst, need), int(obj_size), int(stride),
              int(n_objs), int(dedup), fn, fd, int(seed_base) & (2**64 - 1), int(first_obj),
              self._s(stream))
+
+    # -- verification (synchronous on `stream`) ----------------------------------
+    # The read-side twins of fill_controlled / fill_range / random_data /
+    # fill_stream: the GPU recomputes each 4 KiB block and compares it with the
+    # tensor's bytes, writing nothing.  Same arguments, same bounds check.
+    def _src(self, x, need: int) -> int:
+        return self._dst(x, need, "reads")
+
+    def verify_controlled(self, src, nbytes: int | None = None, dedup: int = 1, compress=1,
+                          entropy: int = 0, stream=None) -> VerifyResult:
+        """Compare `nbytes` at src with fill_controlled's bytes for the same arguments."""
+        n = _nbytes(src) if nbytes is None else int(nbytes)
+        fn, fd = compress_ratio(compress)
+        r = _lib.VerifyRec()
+        call("s3dg_verify_controlled", self._h, self._src(src, n), n, int(dedup), fn, fd,
+             int(entropy) & (2**64 - 1), self._s(stream), ctypes.byref(r))
+        return VerifyResult._of(r)
+
+    def verify_random_data(self, src, nbytes: int | None = None, entropy: int = 0, stream=None) -> VerifyResult:
+        """Compare `nbytes` at src with random_data's bytes for the same arguments."""
+        n = _nbytes(src) if nbytes is None else int(nbytes)
+        r = _lib.VerifyRec()
+        call("s3dg_verify_random_data", self._h, self._src(src, n), n, int(entropy) & (2**64 - 1),
+             self._s(stream), ctypes.byref(r))
+        return VerifyResult._of(r)
+
+    def verify_range(self, src, length: int, blk_lo: int, blk_hi: int, dedup: int = 1,
+                     compress=1, entropy: int = 0, stream=None) -> VerifyResult:
+        """Blocks [blk_lo, blk_hi) of a `length`-byte object, block blk_lo at src;
+        first_offset counts from src."""
+        fn, fd = compress_ratio(compress)
+        hi = min(int(blk_hi) * BLOCK_SIZE, int(length))
+        need = max(0, hi - int(blk_lo) * BLOCK_SIZE)
+        r = _lib.VerifyRec()
+        call("s3dg_verify_controlled_range", self._h, self._src(src, need), int(length), int(blk_lo),
+             int(blk_hi), int(dedup), fn, fd, int(entropy) & (2**64 - 1), self._s(stream), ctypes.byref(r))
+        return VerifyResult._of(r)
+
+    def verify_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None,
+                      dedup: int = 1, compress=1, seed_base: int = 0, first_obj: int = 0,
+                      stream=None) -> VerifyResult:
+        """n_objs equal objects as fill_stream lays them out; counts are summed
+        over the objects, first_offset counts from src (stride gaps included,
+        which are never read)."""
+        stride = obj_size if stride is None else stride
+        need = (int(n_objs) - 1) * int(stride) + int(obj_size) if n_objs > 0 and obj_size > 0 else 0
+        fn, fd = compress_ratio(compress)
+        r = _lib.VerifyRec()
+        call("s3dg_verify_controlled_stream", self._h, self._src(src, need), int(obj_size), int(stride),
+             int(n_objs), int(dedup), fn, fd, int(seed_base) & (2**64 - 1), int(first_obj),
+             self._s(stream), ctypes.byref(r))
+        return VerifyResult._of(r)
 
     def fill_batch(self, dst, objects, stream=None) -> None:
         """objects: iterable of (dst_off, size, entropy, dedup, compress).

@@ -128,6 +128,148 @@ def put_objects(uris, size: int, max_in_flight: int = 64, config: Config | None 
                      int(seed) & (2**64 - 1))
 
 
+@dataclass
+class VerifyObjectsResult:
+    """What verify_objects found: (object index, VerifyResult) of every object
+    that is not clean, in index order, and the totals over all objects."""
+    mismatches: list = field(default_factory=list)
+    objects: int = 0              # objects checked
+    bytes: int = 0                # bytes read and compared
+    mismatched_objects: int = 0
+    mismatched_bytes: int = 0
+    mismatched_blocks: int = 0
+
+    @property
+    def ok(self) -> bool:
+        return not self.mismatches
+
+
+_VERIFY_GROUP_BYTES = 64 << 20   # objects are read and checked in groups of about this size
+
+
+def verify_objects(uris, size: int, config: Config | None = None, seed: int = 0,
+                   payload: str | None = None, context=None) -> VerifyObjectsResult:
+    """Read-side partner of put_objects for file:// RAW objects: read the files
+    back and check on the GPU that object j holds the payload
+    put_objects(uris, size, config=config, seed=seed, payload=payload) wrote
+    for it ("controlled" or "random"; same defaults as put_objects).
+
+    Files are read in groups into pinned host memory, copied to a device chunk
+    and checked there (Context.verify_stream with first_obj = the group's first
+    index; one verify_random_data per object for "random").  A group that is
+    not clean is checked again object by object to name the objects.  A file
+    of the wrong length is a mismatch of that object, not an exception: the
+    whole 4 KiB blocks of the bytes both have are compared, every missing or
+    excess byte counts as mismatched, and first_offset is the lowest differing
+    offset, at most min(actual, expected) length.  A missing file raises.
+    The DG1 payload ("dgen") and framed object types (NPZ, TFRecord) are not
+    supported: there is no verify kernel for the keystream layouts."""
+    import numpy as np
+    from ._lib import c_vp, lib
+    from .device import BLOCK_SIZE, Context, VerifyResult, object_entropy
+    cfg = config or Config.new_with_defaults(ObjectType.RAW, 1, size, 1, 1)
+    if payload is None:
+        payload = "dgen" if cfg.use_controlled else "random"
+    if payload not in _PAYLOADS:
+        raise ValueError(f"unknown payload {payload!r}")
+    if payload == "dgen":
+        raise ValueError('verify_objects checks payload "controlled" or "random" only: the DG1 ("dgen") '
+                         "payload has no verify kernel")
+    if cfg.object_type != ObjectType.RAW:
+        raise ValueError("verify_objects checks RAW objects only: framed object types (NPZ, TFRecord, HDF5) "
+                         "are not supported")
+    paths = [_uri_to_path(u) for u in uris]
+    size = int(size)
+    seed = int(seed) & (2**64 - 1)
+    dedup = max(1, int(cfg.dedup_factor))
+    compress = max(1, int(cfg.compress_factor))
+    out = VerifyObjectsResult()
+    n = len(paths)
+    if n == 0 or size == 0:
+        for j, p in enumerate(paths):   # empty objects: only the length can be wrong
+            actual = os.path.getsize(p)
+            out.objects += 1
+            if actual:
+                out.mismatches.append((j, VerifyResult(actual, 1, 0)))
+        _verify_totals(out)
+        return out
+    ctx = context if context is not None else _contexts([0])[0]
+    stride = (size + 15) & ~15
+    group = max(1, min(n, _VERIFY_GROUP_BYTES // stride))
+    nb = (size + BLOCK_SIZE - 1) // BLOCK_SIZE
+
+    def check(dev, j, k):
+        """Objects [j, j + k) at dev."""
+        if payload == "controlled":
+            return ctx.verify_stream(dev, size, k, stride, dedup, compress, seed, j, stream=st.value)
+        tot = [0, 0, None]
+        for q in range(k):
+            r = ctx.verify_random_data(dev + q * stride, size, object_entropy(seed, j + q), stream=st.value)
+            if not r.ok:
+                tot[0] += r.mismatched_bytes
+                tot[1] += r.mismatched_blocks
+                tot[2] = q * stride + r.first_offset if tot[2] is None else tot[2]
+        return VerifyResult(tot[0], tot[1], tot[2])
+
+    host, dev, st = c_vp(), c_vp(), c_vp()
+    call("s3dg_host_alloc_pinned", group * stride, ctypes.byref(host))
+    try:
+        call("s3dg_device_alloc", ctx._h, group * stride, ctypes.byref(dev))
+        call("s3dg_stream_create", ctx._h, ctypes.byref(st))
+        pinned = np.frombuffer((ctypes.c_uint8 * (group * stride)).from_address(host.value), np.uint8)
+        for j0 in range(0, n, group):
+            k = min(group, n - j0)
+            actual = []
+            for q in range(k):
+                with open(paths[j0 + q], "rb", buffering=0) as f:
+                    got = 0
+                    slot = pinned[q * stride:q * stride + size]
+                    while got < size:
+                        m = f.readinto(slot[got:])
+                        if not m:
+                            break
+                        got += m
+                    actual.append(os.fstat(f.fileno()).st_size)
+                out.bytes += got
+            out.objects += k
+            call("s3dg_h2d_async", ctx._h, dev, host, k * stride, st)
+            if all(a == size for a in actual) and check(dev.value, j0, k).ok:
+                continue
+            for q in range(k):   # name the objects of a group that is not clean
+                a = actual[q]
+                if a >= size:
+                    r = check(dev.value + q * stride, j0 + q, 1)
+                    if a > size:   # excess bytes: one more block
+                        r = VerifyResult(r.mismatched_bytes + a - size, r.mismatched_blocks + 1,
+                                         size if r.ok else r.first_offset)
+                else:              # short: its whole blocks, then every missing byte
+                    full = a // BLOCK_SIZE
+                    if payload == "controlled":
+                        r = ctx.verify_range(dev.value + q * stride, size, 0, full, dedup, compress,
+                                             object_entropy(seed, j0 + q), stream=st.value)
+                    else:
+                        r = ctx.verify_random_data(dev.value + q * stride, full * BLOCK_SIZE,
+                                                   object_entropy(seed, j0 + q), stream=st.value)
+                    r = VerifyResult(r.mismatched_bytes + size - a, r.mismatched_blocks + nb - full,
+                                     a if r.ok else r.first_offset)
+                if not r.ok:
+                    out.mismatches.append((j0 + q, r))
+    finally:
+        if st.value:
+            lib.s3dg_stream_destroy(ctx._h, st)
+        if dev.value:
+            lib.s3dg_device_free(ctx._h, dev)
+        lib.s3dg_host_free_pinned(host)
+    _verify_totals(out)
+    return out
+
+
+def _verify_totals(out: VerifyObjectsResult) -> None:
+    out.mismatched_objects = len(out.mismatches)
+    out.mismatched_bytes = sum(r.mismatched_bytes for _, r in out.mismatches)
+    out.mismatched_blocks = sum(r.mismatched_blocks for _, r in out.mismatches)
+
+
 def put_objects_with_random_data_and_type(uris, size: int, max_in_flight: int, config: Config,
                                           seed: int | None = None) -> PutResult:
     """src/s3_utils.rs:1717-1724 (per-object payloads; see module docstring)."""
