@@ -48,6 +48,7 @@ def lib():
         L.s3dgo_unique_blocks.argtypes = [u64, u64]
         L.s3dgo_unique_blocks.restype = u64
         L.s3dgo_fill_controlled.argtypes = [u8p, u64, u64, u64, u64, u64, u8p]
+        L.s3dgo_fill_controlled_range.argtypes = [u8p, u64, u64, u64, u64, u64, u64, u64, u8p]
         L.s3dgo_object_entropy.argtypes = [u64, u64]
         L.s3dgo_object_entropy.restype = u64
         L.s3dgo_fill_stream.argtypes = [u8p, u64, u64, u64, u64, u64, u64, u64, u64, u8p]
@@ -108,6 +109,20 @@ def fill_controlled(length: int, dedup: int, f_num: int, f_den: int, entropy: in
     out = np.empty(length, np.uint8)
     base = np.ascontiguousarray(base, np.uint8)
     lib().s3dgo_fill_controlled(_ptr(out), length, dedup, f_num, f_den, entropy, _ptr(base))
+    return out
+
+
+def fill_controlled_range(length: int, blk_lo: int, blk_hi: int, dedup: int, f_num: int, f_den: int,
+                          entropy: int, base: np.ndarray) -> np.ndarray:
+    """Blocks [blk_lo, blk_hi) of a `length`-byte object (blk_hi clipped to its end)."""
+    nb = -(-length // 4096)
+    hi = min(blk_hi, nb)
+    n = max(0, min(hi * 4096, length) - blk_lo * 4096)
+    out = np.empty(n, np.uint8)
+    base = np.ascontiguousarray(base, np.uint8)
+    if n:
+        lib().s3dgo_fill_controlled_range(_ptr(out), length, blk_lo, blk_hi, dedup, f_num, f_den,
+                                          entropy & (2**64 - 1), _ptr(base))
     return out
 
 

@@ -112,14 +112,17 @@ def object_entropy(seed_base: int, j: int) -> int:
     return (seed_base + (j << 32)) & M64
 
 
-def fill_controlled(length: int, dedup: int, f_num: int, f_den: int,
-                    entropy: int, base: bytes) -> bytes:
-    if length == 0:
-        return b""
+def fill_controlled_range(length: int, blk_lo: int, blk_hi: int, dedup: int, f_num: int, f_den: int,
+                          entropy: int, base: bytes) -> bytes:
+    """Blocks [blk_lo, blk_hi) of a `length`-byte object (blk_hi clipped to
+    its end); zero-prefix lengths from the closed form, so a range far into a
+    large object costs only its own blocks."""
     nb = -(-length // BLK)
+    if nb == 0:
+        return b""
     U = unique_blocks(nb, dedup)
     out = bytearray()
-    for i in range(nb):
+    for i in range(blk_lo, min(blk_hi, nb)):
         L = min(BLK, length - i * BLK)
         u = i % U
         rng = Xoshiro256pp.seed_from_u64((u + entropy) & M64)
@@ -134,6 +137,32 @@ def fill_controlled(length: int, dedup: int, f_num: int, f_den: int,
                 blk[so:so + m] = rng.fill_bytes(m)
         out += blk
     return bytes(out)
+
+
+def fill_controlled(length: int, dedup: int, f_num: int, f_den: int,
+                    entropy: int, base: bytes) -> bytes:
+    return fill_controlled_range(length, 0, -(-length // BLK), dedup, f_num, f_den, entropy, base)
+
+
+# Zero-prefix ratios (f_num, f_den) with denominators around and far above
+# 2^16, three per denominator (zero prefixes of about 1365, 2730 and 4090
+# bytes).  Given to the library as the coprime tuple (f_den, f_den - f_num).
+WIDE_RATIOS = [
+    (21847, 65535), (43688, 65535), (65446, 65535),
+    (21845, 65536), (43689, 65536), (65447, 65536),
+    (21846, 65537), (43690, 65537), (65448, 65537),
+    (43692, 131071), (87379, 131071), (130893, 131071),
+    (333343, 1000003), (666655, 1000003), (998648, 1000003),
+    (1431694211, 4294967291), (2863252108, 4294967291), (4289147694, 4294967291),
+    (1431694213, 4294967295), (2863252111, 4294967295), (4289147698, 4294967295),
+]
+# reference-semantics integers c -> (c - 1, c): all-zero full blocks (c == L, m == 0)
+WIDE_INTS = [65536, 65537, 100000, 4294967295]
+
+
+def wide_compress(f_num: int, f_den: int) -> tuple[int, int]:
+    """The compress argument (p, q) that maps to (f_num, f_den)."""
+    return (f_den, f_den - f_num)
 
 
 def xoshiro_chunks(length: int, chunk: int, seed_base: int) -> bytes:

@@ -126,15 +126,14 @@ static uint64_t *const_len_table(uint64_t unique, uint64_t f_num, uint64_t f_den
     return v;
 }
 
-/* One 4 KiB block (body of the par_chunks_mut closure, :200-222). */
-static void fill_one_block(uint8_t *chunk, uint64_t len, uint64_t i, uint64_t unique,
-                           const uint64_t *const_lens, uint64_t entropy,
-                           const uint8_t *base) {
-    const uint64_t u = i % unique;
+/* One 4 KiB block (body of the par_chunks_mut closure, :200-222): unique
+ * index u, zero-prefix length const_len of that unique block. */
+static void fill_block_u(uint8_t *chunk, uint64_t len, uint64_t u, uint64_t const_len,
+                         uint64_t entropy, const uint8_t *base) {
     uint64_t s[4];
     s3dgo_xoshiro_seed(s, u + entropy);                 /* wrapping add, :202 */
     memcpy(chunk, base, len);                           /* :205-207 */
-    uint64_t c = const_lens[u] < len ? const_lens[u] : len;
+    uint64_t c = const_len < len ? const_len : len;
     memset(chunk, 0, c);                                /* :209-210 */
     uint64_t region = len - c;
     uint64_t m = region < S3DGO_MOD ? region : S3DGO_MOD;
@@ -143,6 +142,13 @@ static void fill_one_block(uint8_t *chunk, uint64_t len, uint64_t i, uint64_t un
         uint64_t so = c > S3DGO_HALF ? c : S3DGO_HALF;  /* :218 */
         if (so + m <= len) s3dgo_fill_bytes(s, chunk + so, m);   /* :219-221 */
     }
+}
+
+static void fill_one_block(uint8_t *chunk, uint64_t len, uint64_t i, uint64_t unique,
+                           const uint64_t *const_lens, uint64_t entropy,
+                           const uint8_t *base) {
+    const uint64_t u = i % unique;
+    fill_block_u(chunk, len, u, const_lens[u], entropy, base);
 }
 
 void s3dgo_fill_controlled(uint8_t *buf, uint64_t len, uint64_t dedup,
@@ -156,6 +162,43 @@ void s3dgo_fill_controlled(uint8_t *buf, uint64_t len, uint64_t dedup,
         uint64_t off = i * S3DGO_BLK;
         uint64_t l = len - off < S3DGO_BLK ? len - off : S3DGO_BLK;
         fill_one_block(buf + off, l, i, unique, cl, entropy, base);
+    }
+    free(cl);
+}
+
+/* Blocks [blk_lo, blk_hi) of a len-byte object, block blk_lo at buf (blk_hi
+ * past the last block is clipped).  The same accumulator as const_len_table
+ * (src/data_gen.rs:174-190), run once up to the highest unique block the range
+ * maps to; only the lengths of the range's own blocks are kept, so a range of
+ * a multi-GiB object needs neither the object nor a per-block table. */
+void s3dgo_fill_controlled_range(uint8_t *buf, uint64_t len, uint64_t blk_lo, uint64_t blk_hi,
+                                 uint64_t dedup, uint64_t f_num, uint64_t f_den,
+                                 uint64_t entropy, const uint8_t *base) {
+    const uint64_t nblocks = (len + S3DGO_BLK - 1) / S3DGO_BLK;
+    if (blk_hi > nblocks) blk_hi = nblocks;
+    if (blk_lo >= blk_hi) return;
+    const uint64_t unique = s3dgo_unique_blocks(nblocks, dedup);
+    const uint64_t n = blk_hi - blk_lo;
+    uint64_t *cl = (uint64_t *)malloc(sizeof(uint64_t) * n);
+    uint64_t umax = 0;
+    for (uint64_t i = blk_lo; i < blk_hi; ++i)
+        if (i % unique > umax) umax = i % unique;
+    const uint64_t floor_len = (f_num * S3DGO_BLK) / f_den;
+    const uint64_t rem = (f_num * S3DGO_BLK) % f_den;
+    const uint64_t r = blk_lo % unique;
+    uint64_t acc = 0;
+    for (uint64_t k = 0; k <= umax; ++k) {
+        uint64_t v = floor_len;
+        acc += rem;
+        if (acc >= f_den) { acc -= f_den; v = floor_len + 1; }
+        /* the range's blocks i with i % unique == k */
+        for (uint64_t i = blk_lo + (k >= r ? k - r : k + unique - r); i < blk_hi; i += unique)
+            cl[i - blk_lo] = v;
+    }
+    for (uint64_t i = blk_lo; i < blk_hi; ++i) {
+        const uint64_t off = i * S3DGO_BLK;
+        const uint64_t l = len - off < S3DGO_BLK ? len - off : S3DGO_BLK;
+        fill_block_u(buf + (i - blk_lo) * S3DGO_BLK, l, i % unique, cl[i - blk_lo], entropy, base);
     }
     free(cl);
 }

@@ -62,6 +62,12 @@ for d in [4, 7, 16, 100, 1000, 5000]:
     EDGE_CASES.append((40960 + 1, d, 2, 99999))
 EDGE_CASES.append((65536, 1, 1, 2**64 - 3))          # entropy wrap-around in u + E
 EDGE_CASES.append((65536, 2, 3, 2**64 - 1))
+# denominators around and above 2^16 (the kernels' 64-bit closed-form arm), appended
+# so that the earlier cases keep their places
+for c in [P.wide_compress(fn, fd) for fn, fd in P.WIDE_RATIOS] + P.WIDE_INTS:
+    for L in [4096, 4096 * 5 + 123, 40961]:
+        for d in [1, 3]:
+            EDGE_CASES.append((L, d, c, 0xFEDCBA9876543210))
 
 
 def sha(b) -> str:

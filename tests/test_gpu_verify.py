@@ -1,17 +1,24 @@
 """GPU: payload verification (k_verify_stream and the surfaces over it).
 
 Expected bytes always come from the C oracle (oracle/oracle_c.py), never from
-the library's own fill.  A corrupted byte is `^= 0xFF`, so it always differs.
-Every assertion is exact: byte count, block count and first offset.
+the library's own fill.  In sections 1-9 a corrupted byte is `^= 0xFF`, so it
+always differs; sections 10-12 corrupt single bits, every 16-byte piece on its
+own, and seeded random mixes, with the expected result taken from numpy
+(`diff_expect`).  Every assertion is exact: byte count, block count and first
+offset.
 """
 import functools
 import os
+import random
 import threading
 
 import numpy as np
 import pytest
 
+from oracle import oracle_py as P
+
 pytestmark = pytest.mark.gpu
+SOAK = max(1, int(os.environ.get("S3DG_FUZZ_SOAK", "1")))   # soak runs: seeds x SOAK
 
 BLK = 4096
 SIZES = [1, 15, 16, 17, 31, 32, 33, 2047, 2048, 2049, 4095, 4096, 4097, 8292, 3 * 4096 + 2080]
@@ -381,3 +388,159 @@ def test_files(S, gpu_ctx, oracle, base, tmp_path, kind, comp):
         f.write(b"xyz")
     res = S.verify_objects(uris[:1], size, **kw)
     assert res.mismatches == [(0, S.VerifyResult(3, 1, size))]
+
+
+# ---- 10. every bit of a byte -----------------------------------------------------------------------
+
+@pytest.mark.parametrize("waves", [1, 2, 4])
+@pytest.mark.parametrize("compress", [3, (3, 2)], ids=str)
+def test_every_bit(S, torch, wave_ctx, exp, waves, compress):
+    """diff_piece folds a byte's eight bits into one: a byte that differs in
+    bit b only, for each b, is counted once.  Two bytes of one piece, the four
+    bytes of one dword and all sixteen bytes of one piece, in the zero prefix,
+    across the window's start and in the base image of block 1."""
+    ctx = wave_ctx[waves]
+    size, dedup = 3 * BLK + 2080, 2
+    want = exp.controlled(size, dedup, compress, 42)
+    fn, fd = S.compress_ratio(compress)
+    c = P.const_len(1 % S.unique_blocks(4, dedup), fn, fd)
+    assert 32 < c < 3000
+    for piece in (10, c // 16, 250):
+        o = BLK + 16 * piece
+        patterns = {2: [o + 3, o + 12], 4: [o + 8, o + 9, o + 10, o + 11], 16: list(range(o, o + 16))}
+        for bit in range(8):
+            for count, pos in patterns.items():
+                bad = np.array(want, dtype=np.uint8, copy=True)
+                bad[pos] ^= 1 << bit
+                want_r = diff_expect(S, bad, want)
+                assert want_r == S.VerifyResult(count, 1, pos[0])
+                r = ctx.verify_controlled(dev(torch, bad), size, dedup, compress, entropy=42)
+                assert r == want_r, (piece, bit, count, r)
+
+
+# ---- 11. every 16-byte piece, on its own --------------------------------------------------------------
+
+@pytest.mark.parametrize("waves", [1, 2, 4])
+@pytest.mark.parametrize("compress", [3, (3, 2)], ids=str)
+def test_every_piece(S, torch, wave_ctx, exp, waves, compress):
+    """One full block, then a ragged block whose last piece holds 5 bytes: each
+    piece is shown one flipped bit (bit p % 8 of byte p % 16 of piece p), so
+    every lane that owns a piece at this waves-per-block setting reports."""
+    ctx = wave_ctx[waves]
+    size, dedup = BLK + 2085, 1
+    want = exp.controlled(size, dedup, compress, 42)
+    npieces = (size + 15) // 16
+    assert size % 16 == 5 and npieces == 256 + 131
+    flips = [(min(16 * p + p % 16, size - 1), 1 << (p % 8)) for p in range(npieces)]
+    assert len({pos for pos, _ in flips}) == npieces
+    t = dev(torch, want)
+    assert ctx.verify_controlled(t, size, dedup, compress, entropy=42) == S.VerifyResult()
+    for p, (pos, mask) in enumerate(flips):
+        t[pos] ^= mask
+        r = ctx.verify_controlled(t, size, dedup, compress, entropy=42)
+        t[pos] ^= mask
+        assert r == S.VerifyResult(1, 1, pos), (p, pos, r)
+    assert np.array_equal(t.cpu().numpy(), want)
+    bad = np.array(want, dtype=np.uint8, copy=True)
+    for pos, mask in flips:
+        bad[pos] ^= mask
+    want_r = diff_expect(S, bad, want)
+    assert want_r == S.VerifyResult(npieces, 2, flips[0][0])
+    assert ctx.verify_controlled(dev(torch, bad), size, dedup, compress, entropy=42) == want_r
+
+
+# ---- 12. seeded fuzz ------------------------------------------------------------------------------------
+
+def _fuzz_size(rnd):                      # as tests/test_gpu_fuzz.py::_size
+    k = rnd.random()
+    if k < 0.3:
+        return rnd.randint(1, 5000)
+    if k < 0.6:
+        return rnd.choice([4096, 8192, 2048, 2049, 2047]) * rnd.randint(1, 40) + rnd.randint(-7, 7)
+    return rnd.randint(5000, 6 << 20)
+
+
+FUZZ_COMPRESS = [1, 1, 2, 3, 4, 7, 16, (3, 2), (5, 3), (9, 4),
+                 P.wide_compress(43690, 65537), P.wide_compress(1431694211, 4294967291)]
+
+
+def _corrupt(rnd, a):
+    """Corrupt the object `a` (a writable copy of the oracle's bytes) in place
+    by a random mix; what differs afterwards is numpy's to say."""
+    n = a.size
+    mode = rnd.choice(["none", "bits", "bytes", "runs", "mix", "mix"])
+    if mode in ("bits", "mix"):
+        for _ in range(rnd.randint(1, 8)):
+            a[rnd.randrange(n)] ^= 1 << rnd.randrange(8)
+    if mode in ("bytes", "mix"):
+        for _ in range(rnd.randint(1, 8)):
+            a[rnd.randrange(n)] = rnd.randrange(256)      # may be the value already there
+    if mode in ("runs", "mix"):
+        for _ in range(rnd.randint(1, 3)):
+            ln = rnd.randint(1, 40)
+            edge = rnd.choice([16 * rnd.randint(0, n // 16), BLK * rnd.randint(0, n // BLK), n])
+            lo = max(0, min(edge - rnd.randint(0, ln), n - 1))      # the run straddles or touches `edge`
+            hi = min(n, lo + ln)                                    # and stops at the object's end
+            a[lo:hi] = np.frombuffer(rnd.randbytes(hi - lo), np.uint8)
+    return mode
+
+
+@pytest.mark.parametrize("seed", range(8 * SOAK))
+def test_fuzz_verify(S, torch, gpu_ctx, oracle, seed):
+    rnd = random.Random(4000 + seed)
+    orig = gpu_ctx.base_block
+    base = np.frombuffer(rnd.randbytes(BLK), np.uint8).copy()
+    gpu_ctx.set_base_block(base.tobytes())
+    try:
+        for _ in range(4):
+            gpu_ctx.set_waves_per_block(rnd.choice([0, 1, 2, 4]))
+            d, c = rnd.choice([0, 1, 2, 3, 5, 64]), rnd.choice(FUZZ_COMPRESS)
+            fn, fd = S.compress_ratio(c)
+            assert (fn, fd) == P.compress_ratio(c)
+            # one object
+            L, e = _fuzz_size(rnd), rnd.getrandbits(64)
+            want = oracle.fill_controlled(L, d, fn, fd, e, base)
+            got = want.copy()
+            mode = _corrupt(rnd, got)
+            r = gpu_ctx.verify_controlled(dev(torch, got), L, d, c, entropy=e)
+            assert r == diff_expect(S, got, want), ("controlled", L, d, c, e, mode, r)
+            # the random-data layout
+            L, e = _fuzz_size(rnd), rnd.getrandbits(64)
+            want = oracle.random_data(L, e, base)
+            got = want.copy()
+            mode = _corrupt(rnd, got)
+            r = gpu_ctx.verify_random_data(dev(torch, got), L, entropy=e)
+            assert r == diff_expect(S, got, want), ("random", L, e, mode, r)
+            # a block range of an object
+            L, e = _fuzz_size(rnd), rnd.getrandbits(64)
+            nb = (L + BLK - 1) // BLK
+            lo = rnd.randrange(nb)
+            hi = rnd.randint(lo + 1, nb + 2)
+            want = oracle.fill_controlled_range(L, lo, hi, d, fn, fd, e, base)
+            got = want.copy()
+            mode = _corrupt(rnd, got)
+            r = gpu_ctx.verify_range(dev(torch, got), L, lo, hi, d, c, e)
+            assert r == diff_expect(S, got, want), ("range", L, lo, hi, d, c, e, mode, r)
+            # a stream at a padded stride, the gaps poisoned
+            n, sz = rnd.randint(1, 9), _fuzz_size(rnd) % (1 << 20) + 1
+            stride = (sz + 15) // 16 * 16 + 16 * rnd.randint(0, 3)
+            sb, first = rnd.getrandbits(64), rnd.randint(0, 1 << 20)
+            buf = np.frombuffer(rnd.randbytes(n * stride), np.uint8).copy()
+            nbytes, nblocks, first_bad, modes = 0, 0, None, []
+            for j in range(n):
+                want = oracle.fill_controlled(sz, d, fn, fd, P.object_entropy(sb, first + j), base)
+                got = want.copy()
+                modes.append(_corrupt(rnd, got))
+                buf[j * stride:j * stride + sz] = got
+                one = diff_expect(S, got, want)
+                nbytes += one.mismatched_bytes
+                nblocks += one.mismatched_blocks
+                if first_bad is None and not one.ok:
+                    first_bad = j * stride + one.first_offset
+            want_r = S.VerifyResult(nbytes, nblocks, first_bad)
+            r = gpu_ctx.verify_stream(dev(torch, buf), obj_size=sz, n_objs=n, stride=stride, dedup=d, compress=c,
+                                      seed_base=sb, first_obj=first)
+            assert r == want_r, ("stream", sz, n, stride, d, c, sb, first, modes, r, want_r)
+    finally:
+        gpu_ctx.set_base_block(orig)
+        gpu_ctx.set_waves_per_block(0)

@@ -113,7 +113,8 @@ def test_unique_blocks_rounding(oracle, nb, d):
 
 def test_const_len_closed_form_matches_accumulator():
     """The kernels' closed form equals the reference's Bresenham loop."""
-    for (fn, fd) in [(1, 2), (2, 3), (4, 5), (1, 3), (126, 127), (4999, 5000), (2, 5)]:
+    wide = P.WIDE_RATIOS + [(c - 1, c) for c in P.WIDE_INTS]
+    for (fn, fd) in [(1, 2), (2, 3), (4, 5), (1, 3), (126, 127), (4999, 5000), (2, 5)] + wide:
         total = fn * 4096
         floor_len, rem = divmod(total, fd)
         acc, seq = 0, []
@@ -125,6 +126,64 @@ def test_const_len_closed_form_matches_accumulator():
             else:
                 seq.append(floor_len)
         assert [P.const_len(k, fn, fd) for k in range(3000)] == seq
+
+
+def test_wide_ratio_table_inputs():
+    """The wide-ratio table is what the GPU tests assume: coprime pairs (so the
+    (f_den, f_den - f_num) tuple reaches the kernels unreduced), a denominator
+    on each side of the 65536 arm boundary, and both prefix lengths (floor and
+    floor + 1) at least 4 times each among unique blocks 0..15."""
+    import math
+    assert {fd for _, fd in P.WIDE_RATIOS} == {65535, 65536, 65537, 131071, 1000003, 4294967291, 4294967295}
+    for fn, fd in P.WIDE_RATIOS:
+        assert math.gcd(fn, fd) == 1 and P.compress_ratio(P.wide_compress(fn, fd)) == (fn, fd)
+        fl = fn * 4096 // fd
+        assert fl in (1365, 2730, 4090), (fn, fd)
+        lens = [P.const_len(k, fn, fd) for k in range(16)]
+        assert lens.count(fl) >= 4 and lens.count(fl + 1) >= 4 and lens.count(fl) + lens.count(fl + 1) == 16, (fn, fd)
+
+
+RANGE_RATIOS = [(0, 1), (1, 2), (2, 3), (2, 5)] + P.WIDE_RATIOS + [(c - 1, c) for c in P.WIDE_INTS]
+
+
+@pytest.mark.parametrize("dedup", [0, 1, 2, 3, 7])
+def test_range_equals_slice_of_fill_controlled(oracle, golden_base, dedup):
+    """fill_controlled_range is the matching slice of the whole object, in both
+    oracles, clipped at the ragged end; an empty range gives nothing."""
+    base = np.frombuffer(golden_base, np.uint8)
+    for k, (fn, fd) in enumerate(RANGE_RATIOS):
+        for length in (1, 4096, 4097, 11 * 4096 + 123):
+            nb = -(-length // 4096)
+            e = 0x0123456789ABCDEF + k
+            whole = oracle.fill_controlled(length, dedup, fn, fd, e, base)
+            assert P.fill_controlled(length, dedup, fn, fd, e, golden_base) == bytes(whole)
+            for lo, hi in {(0, nb), (0, 1), (nb - 1, nb), (nb - 1, nb + 5), (1, 4), (3, 9), (5, 12), (2, 2), (nb, nb + 1)}:
+                want = bytes(whole[lo * 4096:min(hi, nb) * 4096]) if lo < min(hi, nb) else b""
+                got = oracle.fill_controlled_range(length, lo, hi, dedup, fn, fd, e, base)
+                assert bytes(got) == want, (length, lo, hi, fn, fd)
+                assert P.fill_controlled_range(length, lo, hi, dedup, fn, fd, e, golden_base) == want, (length, lo, hi)
+
+
+@pytest.mark.parametrize("dedup", [1, 3])
+def test_range_c_equals_python_at_large_block_indices(oracle, golden_base, dedup):
+    """C (literal accumulator run up to the highest unique block) against
+    Python (closed form) far into a (2^24 + 3)-block object: around block
+    65 536, where the unique index passes the small denominators, and at the
+    ragged end past 2^24 (and, with dedup 3, across the i % U wrap)."""
+    base = np.frombuffer(golden_base, np.uint8)
+    nb = (1 << 24) + 3
+    length = (nb - 1) * 4096 + 77
+    U = P.unique_blocks(nb, dedup)
+    ranges = [(65535, 65541), ((1 << 24) - 2, nb + 4)]
+    if dedup == 3:
+        ranges += [(U - 3, U + 3), (2 * U - 2, 2 * U + 2)]
+    for fn, fd in [(1, 2), (65446, 65535), (21845, 65536), (43690, 65537), (87379, 131071),
+                   (666655, 1000003), (1431694211, 4294967291), (4289147698, 4294967295), (99999, 100000)]:
+        for lo, hi in ranges:
+            got = oracle.fill_controlled_range(length, lo, hi, dedup, fn, fd, 2**64 - 5, base)
+            assert got.size == min(hi * 4096, length) - lo * 4096
+            assert bytes(got) == P.fill_controlled_range(length, lo, hi, dedup, fn, fd, 2**64 - 5, golden_base), \
+                (lo, hi, fn, fd)
 
 
 def test_mt_equals_single_thread(oracle, golden_base):

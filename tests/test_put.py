@@ -115,6 +115,15 @@ def _dump_failure(oracle, kind, t, size, d, c, seed, j, got, pay, bad):
     ("dgen", "TFRECORD", 1, 300 * MiB + 7, 1, 4),     # split, DG1 pieces on 1 MiB blocks
     ("random", "RAW", 3, 4096, 1, 1),
     ("controlled", "NPZ", 4, 1, 1, 1),
+    # CRC segments of 1, 2 and 3 whole 1 KiB rows (the single-row loop alone), and 32-row
+    # regions followed by a last region of 1, 2 and 3 rows (crc_seg_fold's x_last)
+    # (compress 1: a zero prefix would make those rows all zero, whose raw CRC is 0 whatever the kernel does)
+    ("controlled", "RAW", 9, 1024 + 7, 1, 1),
+    ("controlled", "RAW", 9, 2048, 2, 1),
+    ("controlled", "RAW", 9, 3 * 1024 + 1023, 1, 1),
+    ("controlled", "RAW", 9, 33 * 1024 + 1, 3, 1),
+    ("controlled", "RAW", 9, 34 * 1024, 1, 1),
+    ("controlled", "RAW", 9, 35 * 1024 + 513, 2, 1),
 ])
 def test_gpu_put_round_trip(S, oracle, golden_base, gpu_ctx, tmp_path, kind, t, n, size, d, c):
     uris = [f"file://{tmp_path}/sub/dir/obj-{j}" for j in range(n)]
