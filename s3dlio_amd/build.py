@@ -4,8 +4,9 @@
 
 (run it by path: `python -m` would import the package, i.e. load the old .so)
 
-Plain hipcc, no CMake: two translation units (kernels + C ABI) linked into
-one .so that exports exactly the symbols of include/s3dlio_gpu.h.
+Plain hipcc, no CMake: one translation unit per file of SOURCES (the kernels
+in the .hip files, the C ABI over them split by concern in the .cpp files),
+linked into one .so that exports exactly the symbols of include/s3dlio_gpu.h.
 """
 from __future__ import annotations
 
@@ -18,12 +19,15 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libs3dlio_amd.so")
 SOURCES = [os.path.join(CSRC, "s3dg_kernels.hip"), os.path.join(CSRC, "s3dg_capi.cpp"),
+           os.path.join(CSRC, "s3dg_tune.cpp"), os.path.join(CSRC, "s3dg_fill.cpp"),
+           os.path.join(CSRC, "s3dg_batchfill.cpp"), os.path.join(CSRC, "s3dg_keystream.cpp"),
            os.path.join(CSRC, "s3dg_jump.cpp"), os.path.join(CSRC, "s3dg_generator.cpp"),
            os.path.join(CSRC, "s3dg_crc.hip"), os.path.join(CSRC, "s3dg_npz.cpp"),
            os.path.join(CSRC, "s3dg_object.cpp"), os.path.join(CSRC, "s3dg_put.cpp"),
            os.path.join(CSRC, "s3dg_numa.cpp"), os.path.join(CSRC, "s3dg_host.cpp"),
            os.path.join(CSRC, "s3dg_batch.hip")]
-HEADERS = [os.path.join(CSRC, "s3dg_internal.h"), os.path.join(CSRC, "s3dg_jump.h"),
+HEADERS = [os.path.join(CSRC, "s3dg_internal.h"), os.path.join(CSRC, "s3dg_ctx.h"),
+           os.path.join(CSRC, "s3dg_batch_plan.h"), os.path.join(CSRC, "s3dg_jump.h"),
            os.path.join(ROOT, "include", "s3dlio_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

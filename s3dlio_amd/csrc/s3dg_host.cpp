@@ -816,6 +816,21 @@ static int controlled_job(HostJob &J, uint64_t len, uint64_t dedup, uint64_t com
     return make_prefix((len + kBlk - 1) / kBlk, dedup, fn, fd, &J.pp);
 }
 
+// generate_random_data payload for generate_object: seeded (the slot
+// context's default base block, entropy = seed) or unseeded (time entropy +
+// the per-process BASE_BLOCK).
+int random_host(uint8_t *buf, uint64_t len, uint64_t entropy, int use_process_base) {
+    if (len == 0) return S3DG_OK;
+    const uint64_t nb = (len + kBlk - 1) / kBlk;
+    if (nb > 0xFFFFFFFFull) return s3dg_internal_fail(S3DG_EINVAL, "object larger than 2^32 blocks");
+    HostJob J;
+    J.obj_len = len;
+    J.pp = random_layout_prefix();
+    J.entropy = use_process_base ? time_entropy() : entropy;
+    J.base = use_process_base ? HostJob::kBaseProcB : HostJob::kBaseCtx;
+    return host_oneshot(J, buf, len);
+}
+
 }  // namespace s3dg
 
 extern "C" {
@@ -903,25 +918,10 @@ int s3dg_host_slot_context(int slot, s3dg_ctx **out) {
     return S3DG_OK;
 }
 
-// generate_random_data payload for generate_object: seeded (the slot
-// context's default base block, entropy = seed) or unseeded (time entropy +
-// the per-process BASE_BLOCK).
-int s3dg_internal_random_host(uint8_t *buf, uint64_t len, uint64_t entropy, int use_process_base) {
-    if (len == 0) return S3DG_OK;
-    const uint64_t nb = (len + kBlk - 1) / kBlk;
-    if (nb > 0xFFFFFFFFull) return s3dg_internal_fail(S3DG_EINVAL, "object larger than 2^32 blocks");
-    HostJob J;
-    J.obj_len = len;
-    J.pp = random_layout_prefix();
-    J.entropy = use_process_base ? time_entropy() : entropy;
-    J.base = use_process_base ? HostJob::kBaseProcB : HostJob::kBaseCtx;
-    return host_oneshot(J, buf, len);
-}
-
 int s3dlio_generate_random_data(uint8_t *buf, size_t size) {
     if (size == 0) return S3DG_OK;
     if (!buf) return s3dg_internal_fail(S3DG_EINVAL, "null buffer");
-    return s3dg_internal_random_host(buf, size, 0, 1);
+    return random_host(buf, size, 0, 1);
 }
 
 int s3dlio_fill_controlled_data(uint8_t *buf, size_t len, size_t dedup, size_t compress) {

@@ -4,26 +4,20 @@
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 
-#include "s3dlio_gpu.h"
+#include <vector>
 
+#include "s3dlio_gpu.h"
+#include "s3dg_batch_plan.h"   // kBlk, the batch tile-shift range
+
+// Sets the calling thread's error text (s3dg_last_error) and returns code.
 extern "C" int s3dg_internal_fail(int code, const char *msg);
 struct s3dg_ctx;
 
 namespace s3dg {
 
-constexpr uint32_t kBlk = 4096;   // BLK_SIZE   src/constants.rs:326
 constexpr uint32_t kHalf = 2048;  // HALF_BLK   src/constants.rs:329
 constexpr uint32_t kMod = 32;     // MOD_SIZE   src/constants.rs:352
 constexpr uint64_t kDgenBlock = 1ull << 20;   // DGEN_BLOCK_SIZE src/constants.rs:348
-// batch tiles (tile -> object map granule) are 2^tshift blocks, tshift in
-// [kTileShiftMin, kTileShiftMax], chosen per launch (s3dg_capi.cpp pick_tile_shift)
-constexpr uint32_t kTileShiftMin = 1, kTileShiftMax = 6;
-// the per-launch choice considers 8..64-block tiles only: 2- and 4-block tiles
-// (s3dg_set_batch_tile) cut dead slots but lose more to records, e.g. 16-B
-// packed 20 KiB objects 2556 vs 2917 GB/s (profiles/r02/diag/desc40/ab3_*.log)
-constexpr uint32_t kTileShiftAutoMin = 3;
-// tshift 0 (one record per 4 KiB granule of the batch's address range, no
-// per-object lead) is the dense layout for small packed objects
 constexpr int kWavesPerWG = 4;
 
 // Zero-prefix parameters of one object: const_len(u) =
@@ -207,7 +201,7 @@ hipError_t launch_write_ceiling(const LaunchCfg &lc, uint8_t *dst, uint64_t len,
                                 uint32_t pattern, const TileRec *thr, uint64_t nthr, hipStream_t s);
 
 
-// ---- context internals (s3dg_capi.cpp) ---------------------------------------
+// ---- context internals (s3dg_capi.cpp; the context's fields: s3dg_ctx.h) -----
 // Zero-prefix parameters of an object of nblocks 4 KiB blocks
 // (src/data_gen.rs:162-190); S3DG_EINVAL on a bad ratio.
 int make_prefix(uint64_t nblocks, uint64_t dedup, uint32_t f_num, uint32_t f_den, PrefixParams *pp);
@@ -215,6 +209,25 @@ int make_prefix(uint64_t nblocks, uint64_t dedup, uint32_t f_num, uint32_t f_den
 PrefixParams random_layout_prefix();
 LaunchCfg ctx_stream_cfg(const s3dg_ctx *c);   // the context's stream-kernel launch knobs
 const void *ctx_base(const s3dg_ctx *c);       // the context's 4 KiB base block in HBM
+// The context's device (callers make it current with a DeviceScope).
+int ctx_device(s3dg_ctx *c, int *dev);
+
+// ---- chunks of the put pipeline (s3dg_fill.cpp, s3dg_keystream.cpp) ----------
+// Chunk of n_objs equal objects for the put pipeline: blocks [blk_lo, blk_hi)
+// of objects first_obj..first_obj+n_objs-1, object k's block blk_lo at
+// dst + k*stride; controlled layout or (random_layout) generate_random_data's.
+int fill_chunk(s3dg_ctx *c, void *dst, uint64_t obj_size, uint64_t stride, uint64_t n_objs, uint64_t blk_lo,
+               uint64_t blk_hi, int random_layout, uint64_t dedup, uint32_t f_num, uint32_t f_den,
+               uint64_t seed_base, uint64_t first_obj, void *stream);
+// n_objs equal DG1 objects in one launch: blocks [blk_lo, blk_hi) of object
+// first_obj + k at dst + k*stride, seeded object_entropy(seed_base, first_obj + k).
+int dgen_chunk(s3dg_ctx *c, void *dst, uint64_t obj_size, uint64_t stride, uint64_t n_objs, uint64_t blk_lo,
+               uint64_t blk_hi, uint64_t dedup, uint32_t f_num, uint32_t f_den, uint64_t seed_base,
+               uint64_t first_obj, void *stream);
+
+// ---- object assembly (s3dg_object.cpp) ---------------------------------------
+void object_frame(int type, uint64_t elements, uint64_t len, uint32_t pcrc, std::vector<uint8_t> &pre,
+                  std::vector<uint8_t> &suf);
 
 // ---- host-buffer engine (s3dg_host.cpp) --------------------------------------
 // Pinned host allocations made by this library (s3dg_host_alloc_pinned[_local]
@@ -268,6 +281,10 @@ int host_run_split(HostStaging *sg0, const HostJob &J, uint8_t *buf, uint64_t po
 // staging set's slot; the caller's base block must already be in place.
 int host_launch_blocks(HostStaging *sg, const HostJob &J, uint8_t *dst, uint64_t b_lo, uint64_t b_hi,
                        hipStream_t st);
+// generate_random_data payload for generate_object: seeded (the slot
+// context's default base block, entropy = seed) or unseeded (time entropy +
+// the per-process BASE_BLOCK).
+int random_host(uint8_t *buf, uint64_t len, uint64_t entropy, int use_process_base);
 
 // Read-ahead ring of a streaming generator (s3dg_generator.cpp): 2 halves of
 // `half` bytes of pinned host memory on the slot's NUMA node, written by the
@@ -286,6 +303,9 @@ void host_ring_release(HostRing *r);   // the caller has waited for its pending 
 // ---- CRC-32 (s3dg_crc.hip) -------------------------------------------------
 uint32_t crc32_host_update(uint32_t crc, const uint8_t *p, uint64_t n);
 uint32_t crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2);
+// CRC-32 of dev[0, len) (one segment): device regions + host fold + host tail.
+hipError_t crc32_device(const uint8_t *dev, uint64_t len, hipStream_t s, uint32_t *out, void **tab_cache,
+                        uint32_t **seg_cache, uint64_t *seg_cap);
 
 // nseg equal segments of seg_len bytes at seg_stride: whole 1 KiB rows are
 // hashed on the device (nreg regions of `rows` rows), the < 1 KiB tail of

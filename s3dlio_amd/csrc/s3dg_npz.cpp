@@ -12,17 +12,6 @@
 #include <string>
 #include <vector>
 
-namespace s3dg {
-uint32_t crc32_host_update(uint32_t crc, const uint8_t *p, uint64_t n);
-uint32_t crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2);
-hipError_t crc32_device(const uint8_t *dev, uint64_t len, hipStream_t s, uint32_t *out,
-                        void **tab_cache, uint32_t **seg_cache, uint64_t *seg_cap);
-}  // namespace s3dg
-
-extern "C" int s3dg_internal_fail(int code, const char *msg);
-struct s3dg_ctx;
-extern "C" int s3dg_internal_ctx_device(s3dg_ctx *c, int *dev);
-
 namespace {
 
 using namespace s3dg;
@@ -116,11 +105,7 @@ Layout layout(const uint64_t *shape, int ndim, const std::string &dtype, uint64_
 
 }  // namespace
 
-struct s3dg_ctx;
 extern "C" {
-int s3dg_xoshiro_fill(s3dg_ctx *ctx, void *dst, uint64_t len, uint64_t chunk_bytes, uint64_t seed_base,
-                      void *stream);
-int s3dg_internal_crc_device(s3dg_ctx *ctx, const void *dev, uint64_t len, void *stream, uint32_t *out);
 
 int s3dg_npz_size(const uint64_t *shape, int ndim, const char *dtype, uint64_t num_samples,
                   uint64_t *total) {
@@ -153,7 +138,7 @@ int s3dg_npz_build(s3dg_ctx *ctx, const uint64_t *shape, int ndim, const char *d
         static std::mutex map_mu;
         static std::map<int, Cache *> *caches = new std::map<int, Cache *>();   // never freed: outlives HIP
         int device = 0;
-        if (int r = s3dg_internal_ctx_device(ctx, &device)) return r;
+        if (int r = ctx_device(ctx, &device)) return r;
         DeviceScope ds(device);
         if (!ds.ok()) return s3dg_internal_fail(S3DG_EHIP, "hipSetDevice");
         Cache *C;

@@ -18,11 +18,6 @@
 #include <string>
 #include <vector>
 
-
-extern "C" int s3dg_internal_fail(int code, const char *msg);
-extern "C" int s3dg_internal_random_host(uint8_t *buf, uint64_t len, uint64_t entropy,
-                                         int use_process_base);
-
 namespace {
 
 using namespace s3dg;
@@ -176,7 +171,7 @@ int s3dg_generate_object(int type, uint64_t elements, uint64_t element_size, int
     if (total) {
         int r;
         if (!use_controlled)                                               // :66-69
-            r = s3dg_internal_random_host(payload, total, seed, has_seed ? 0 : 1);
+            r = random_host(payload, total, seed, has_seed ? 0 : 1);
         else {
             // Streaming (:40-51) and SinglePass (:52-64) produce the same
             // dgen-contract bytes here; `mode` only selects how the reference

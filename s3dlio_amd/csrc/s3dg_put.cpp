@@ -47,22 +47,6 @@
 #include <thread>
 #include <vector>
 
-extern "C" int s3dg_internal_ctx_device(s3dg_ctx *c, int *dev);
-extern "C" int s3dg_internal_dgen_chunk(s3dg_ctx *c, void *dst, uint64_t obj_size, uint64_t stride,
-                                        uint64_t n_objs, uint64_t blk_lo, uint64_t blk_hi, uint64_t dedup,
-                                        uint32_t f_num, uint32_t f_den, uint64_t seed_base,
-                                        uint64_t first_obj, void *stream);
-extern "C" int s3dg_internal_fill_chunk(s3dg_ctx *c, void *dst, uint64_t obj_size, uint64_t stride,
-                                        uint64_t n_objs, uint64_t blk_lo, uint64_t blk_hi,
-                                        int random_layout, uint64_t dedup, uint32_t f_num,
-                                        uint32_t f_den, uint64_t seed_base, uint64_t first_obj,
-                                        void *stream);
-
-namespace s3dg {
-void object_frame(int type, uint64_t elements, uint64_t len, uint32_t pcrc, std::vector<uint8_t> &pre,
-                  std::vector<uint8_t> &suf);
-}  // namespace s3dg
-
 namespace {
 
 using namespace s3dg;
@@ -371,13 +355,13 @@ int run_lane(const PutArgs &A, s3dg_ctx *ctx, PutPool &P, int lane, uint64_t j0,
         uint8_t *d = (uint8_t *)P.dev[ds];
         if (A.payload == S3DG_PAYLOAD_DGEN) {        // one launch for the whole chunk
             const uint64_t b0 = c.off / kDgenBlock, b1 = (c.off + c.len + kDgenBlock - 1) / kDgenBlock;
-            if (int r = s3dg_internal_dgen_chunk(ctx, d, size, stride, c.n_objs, c.piece ? b0 : 0,
+            if (int r = dgen_chunk(ctx, d, size, stride, c.n_objs, c.piece ? b0 : 0,
                                                  c.piece ? b1 : nbD, A.dedup, A.f_num, A.f_den, A.seed_base,
                                                  c.first_obj, s))
                 return r;
         } else {
             const uint64_t b0 = c.off / kBlk, b1 = (c.off + c.len + kBlk - 1) / kBlk;
-            if (int r = s3dg_internal_fill_chunk(ctx, d, size, stride, c.n_objs, b0, b1,
+            if (int r = fill_chunk(ctx, d, size, stride, c.n_objs, b0, b1,
                                                  A.payload == S3DG_PAYLOAD_RANDOM, A.dedup, A.f_num, A.f_den,
                                                  A.seed_base, c.first_obj, s))
                 return r;
@@ -510,7 +494,7 @@ extern "C" int s3dg_put_objects_multi(s3dg_ctx *const *ctxs, uint32_t nctx, cons
     std::vector<std::unique_lock<std::mutex>> locks;
     std::map<int, int> lane_of_dev;
     for (uint32_t k = 0; k < L; ++k) {
-        if (int r = s3dg_internal_ctx_device(ctxs[k], &devs[k])) return r;
+        if (int r = ctx_device(ctxs[k], &devs[k])) return r;
         pools[k] = &pool(devs[k], lane_of_dev[devs[k]]++);
     }
     for (uint32_t k = 0; k < L; ++k) {

@@ -43,7 +43,7 @@ def build():
           "    const uint64_t wi_ = bid * W + w;\n"
           "    const uint64_t gl = A.xres ? (((wi_ >> 3) << lsh) + (wi_ & 7) + 8 * (uint64_t)l) : wi_ * 64 + l;")
     patch(os.path.join(c, "s3dg_kernels.hip"), "        X.xg = xg;", "        X.xg = X.xres ? 1 : xg;")
-    patch(os.path.join(c, "s3dg_capi.cpp"), "    A.lpc = lpc;\n    A.span = (uint32_t)span;\n    A.z0 = z0;",
+    patch(os.path.join(c, "s3dg_keystream.cpp"), "    A.lpc = lpc;\n    A.span = (uint32_t)span;\n    A.z0 = z0;",
           "    A.lpc = lpc;\n    A.span = (uint32_t)span;\n    A.z0 = z0;\n"
           "    A.xres = getenv(\"S3DG_KS_XRES\") && mode == 0 && lpc == 512 && z0 == 0 ? 1u : 0u;")
     sys.path.insert(0, os.path.join(ROOT, "s3dlio_amd"))

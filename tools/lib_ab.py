@@ -36,7 +36,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "tools", "_build")
 DEFAULT = "r02=aa93058;r03=dedd5d0;head=."
-SRC_NAMES = ["s3dg_kernels.hip", "s3dg_capi.cpp", "s3dg_jump.cpp", "s3dg_generator.cpp", "s3dg_crc.hip",
+SRC_NAMES = ["s3dg_kernels.hip", "s3dg_capi.cpp", "s3dg_tune.cpp", "s3dg_fill.cpp", "s3dg_batchfill.cpp",
+             "s3dg_keystream.cpp", "s3dg_jump.cpp", "s3dg_generator.cpp", "s3dg_crc.hip",
              "s3dg_npz.cpp", "s3dg_object.cpp", "s3dg_put.cpp", "s3dg_numa.cpp", "s3dg_host.cpp", "s3dg_batch.hip"]
 
 
