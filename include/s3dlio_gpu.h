@@ -289,6 +289,30 @@ int s3dg_verify_controlled_stream(s3dg_ctx *ctx, const void *src, uint64_t obj_s
                                   uint64_t n_objs, uint64_t dedup, uint32_t f_num, uint32_t f_den,
                                   uint64_t seed_base, uint64_t first_obj, void *stream,
                                   s3dg_verify_result *out);
+/* The read-side twins of s3dg_xoshiro_fill / s3dg_dgen_fill /
+ * s3dg_dgen_fill_stream (the keystream layouts: the npz x-fill and DG1), under
+ * the same rules as the calls above: the GPU regenerates each chunk's keystream
+ * (seed, jump, draws, the 1-4-byte tail draw, DG1's zero prefix) with the
+ * fill's own code and compares it with `src`; no store, and no byte of a
+ * stride gap or past the last object is read.  Arguments, seeds and
+ * S3DG_EINVAL cases are the fill's (16-byte aligned `src` and `stride`,
+ * f_num < f_den, at most 2^32 blocks, overlapping strides refused); an empty
+ * input or block range launches nothing and is clean.  mismatched_blocks
+ * counts 4 KiB granules aligned within each object (xoshiro: within the
+ * buffer), so the struct reads the same for every layout.
+ * One difference from the fill: s3dg_verify_xoshiro needs chunk_bytes to be a
+ * positive multiple of 4096 (every chunk then starts on a granule; the npz
+ * fill's chunks are 2 MiB) and refuses other values with S3DG_EINVAL, where
+ * s3dg_xoshiro_fill takes any multiple of 128. */
+int s3dg_verify_xoshiro(s3dg_ctx *ctx, const void *src, uint64_t len, uint64_t chunk_bytes,
+                        uint64_t seed_base, void *stream, s3dg_verify_result *out);
+int s3dg_verify_dgen(s3dg_ctx *ctx, const void *src, uint64_t obj_size, uint64_t blk_lo, uint64_t blk_hi,
+                     uint64_t dedup, uint32_t f_num, uint32_t f_den, uint64_t seed, void *stream,
+                     s3dg_verify_result *out);
+int s3dg_verify_dgen_stream(s3dg_ctx *ctx, const void *src, uint64_t obj_size, uint64_t stride,
+                            uint64_t n_objs, uint64_t dedup, uint32_t f_num, uint32_t f_den,
+                            uint64_t seed_base, uint64_t first_obj, void *stream,
+                            s3dg_verify_result *out);
 
 /* ---- memory / copy helpers ------------------------------------------------ */
 int s3dg_device_alloc(s3dg_ctx *ctx, uint64_t bytes, void **out);
@@ -381,6 +405,15 @@ int s3dg_gen_reset(s3dg_gen *gen);
 /* generate_data / generate_controlled_data_alt one-shot into buf. */
 int s3dg_generate_data(uint8_t *buf, uint64_t size, uint64_t dedup, uint64_t compress,
                        int has_seed, uint64_t seed);
+/* The read-side twin of s3dg_generate_data(buf, size, dedup, compress, 1, seed),
+ * and of whatever a seeded generator wrote into buf in whatever chunk sizes
+ * (generation is positional): compares buf[0, size) with that object's bytes
+ * on a host slot's GPU (H2D in 64 MiB chunks on two streams, each verified as
+ * a DG1 block range into one device record).  buf may have any alignment and
+ * be read-only; nothing is written to it.  size 0: clean, no GPU touched; a
+ * null `out` is S3DG_EINVAL.  On an error no copy is still reading buf. */
+int s3dg_verify_generated_data(const uint8_t *buf, uint64_t size, uint64_t dedup, uint64_t compress,
+                               uint64_t seed, s3dg_verify_result *out);
 
 /* ---- object assembly: generate_object (src/data_gen.rs:29-94) ------------ */
 enum { S3DG_OBJ_NPZ = 0, S3DG_OBJ_TFRECORD = 1, S3DG_OBJ_HDF5 = 2, S3DG_OBJ_RAW = 3 };

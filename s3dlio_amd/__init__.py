@@ -11,7 +11,8 @@ from .device import (BLOCK_SIZE, DEFAULT_BASE_SEED, Context, VerifyResult, compr
                      device_count, host_context, host_slots, object_entropy, parse_devices,
                      unique_blocks, xoshiro_jump)
 from .data_gen import (HostRegistration, fill_controlled_data, fill_controlled_data_seeded,  # noqa: F401
-                       register_host_buffer, unregister_host_buffer, verify_controlled_data_seeded)
+                       register_host_buffer, unregister_host_buffer, verify_controlled_data_seeded,
+                       verify_generated_data)
 from .datagen import (DataGenerator, Generator, ObjectGen, default_data_gen_threads,  # noqa: F401
                       generate_controlled_data_alt, generate_controlled_data_streaming,
                       generate_data, generate_data_with_threads, generate_into_buffer,

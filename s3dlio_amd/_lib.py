@@ -97,6 +97,11 @@ SIGNATURES = {
     "s3dg_verify_random_data": (c_int, [c_vp, c_vp, c_u64, c_u64, c_vp, ctypes.POINTER(VerifyRec)]),
     "s3dg_verify_controlled_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_u64, c_u32, c_u32,
                                               c_u64, c_u64, c_vp, ctypes.POINTER(VerifyRec)]),
+    "s3dg_verify_xoshiro": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp, ctypes.POINTER(VerifyRec)]),
+    "s3dg_verify_dgen": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_u64, c_u32, c_u32, c_u64, c_vp,
+                                 ctypes.POINTER(VerifyRec)]),
+    "s3dg_verify_dgen_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_u64, c_u32, c_u32, c_u64, c_u64, c_vp,
+                                        ctypes.POINTER(VerifyRec)]),
     "s3dg_write_ceiling": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
     "s3dg_write_ceiling_tiled": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
     "s3dg_write_ceiling_fill": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
@@ -126,6 +131,7 @@ SIGNATURES = {
     "s3dg_host_slot_device": (c_int, [c_int, ctypes.POINTER(c_int)]),
     "s3dg_host_slot_context": (c_int, [c_int, ctypes.POINTER(c_vp)]),
     "s3dg_generate_data": (c_int, [c_vp, c_u64, c_u64, c_u64, c_int, c_u64]),
+    "s3dg_verify_generated_data": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, ctypes.POINTER(VerifyRec)]),
     "s3dg_crc32": (c_int, [c_vp, c_vp, c_u64, c_vp, ctypes.POINTER(c_u32)]),
     "s3dg_crc32_combine": (c_u32, [c_u32, c_u32, c_u64]),
     "s3dg_crc32_host": (c_u32, [c_u32, c_vp, c_u64]),

@@ -27,7 +27,8 @@ SOURCES = [os.path.join(CSRC, "s3dg_kernels.hip"), os.path.join(CSRC, "s3dg_capi
            os.path.join(CSRC, "s3dg_numa.cpp"), os.path.join(CSRC, "s3dg_host.cpp"),
            os.path.join(CSRC, "s3dg_batch.hip")]
 HEADERS = [os.path.join(CSRC, "s3dg_internal.h"), os.path.join(CSRC, "s3dg_ctx.h"),
-           os.path.join(CSRC, "s3dg_batch_plan.h"), os.path.join(CSRC, "s3dg_jump.h"),
+           os.path.join(CSRC, "s3dg_batch_plan.h"), os.path.join(CSRC, "s3dg_ks_verify_plan.h"),
+           os.path.join(CSRC, "s3dg_jump.h"),
            os.path.join(ROOT, "include", "s3dlio_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

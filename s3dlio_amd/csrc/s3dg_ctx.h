@@ -6,6 +6,7 @@
 #pragma once
 #include "s3dg_internal.h"
 
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -316,6 +317,13 @@ int tune_pick(s3dg_ctx *c, int zc, uint64_t bytes, bool *timed, ZcTuner::Pending
 // its events go straight back to the spares (its near-zero elapsed
 // time would otherwise enter the medians as a huge GB/s sample).
 void tune_mark(s3dg_ctx *c, int zc, const ZcTuner::Pending &probe, bool end, hipStream_t s, bool launched = true);
+
+// A synchronous verify call on stream s (s3dg_fill.cpp): a result record of
+// the call's own from the context's idle list, reset on the stream;
+// launch(rec) enqueues the compare kernels that add to it; the record is
+// copied back, the stream drained, the record returned to the list.
+int verify_with_record(s3dg_ctx *c, hipStream_t s, const char *launch_what,
+                       const std::function<hipError_t(VerifyRec *)> &launch, s3dg_verify_result *out);
 
 // A record map of at least `tiles` records in place of *map (s3dg_fill.cpp).
 // The caller has waited for every launch that reads the old one.

@@ -155,12 +155,15 @@ int s3dg_fill_controlled_stream(s3dg_ctx *c, void *dst, uint64_t obj_size, uint6
 }
 
 // ---- verification (k_verify_stream) -------------------------------------------
+}  // extern "C"
+
+namespace s3dg {
+
 // One call: a result record of its own (from the context's idle list, so two
 // threads on two streams never share one), reset on the stream, the launch,
 // the record copied back, the stream drained.
-static int verify_run(s3dg_ctx *c, const void *src, uint64_t obj_size, uint64_t stride, uint64_t n_objs,
-                      uint64_t blk_lo, uint64_t blk_hi, uint64_t seed_base, uint64_t first_obj,
-                      const PrefixParams &pp, hipStream_t s, s3dg_verify_result *out) {
+int verify_with_record(s3dg_ctx *c, hipStream_t s, const char *launch_what,
+                       const std::function<hipError_t(VerifyRec *)> &launch, s3dg_verify_result *out) {
     VerifyRec *rec = nullptr;
     {
         std::lock_guard<std::mutex> g(c->mu);
@@ -174,9 +177,8 @@ static int verify_run(s3dg_ctx *c, const void *src, uint64_t obj_size, uint64_t 
     hipError_t e = verify_rec_reset(rec, s);
     const char *what = "hipMemsetAsync(verify record)";
     if (e == hipSuccess) {
-        e = launch_verify_stream(cfg_for(c), (const uint8_t *)src, obj_size, stride, n_objs, (uint32_t)blk_lo,
-                                 (uint32_t)blk_hi, seed_base, first_obj, pp, c->base_dev, 0, rec, s);
-        what = "launch k_verify_stream";
+        e = launch(rec);
+        what = launch_what;
     }
     if (e == hipSuccess) {
         e = hipMemcpyAsync(&host, rec, sizeof(host), hipMemcpyDeviceToHost, s);
@@ -197,6 +199,19 @@ static int verify_run(s3dg_ctx *c, const void *src, uint64_t obj_size, uint64_t 
     out->mismatched_blocks = host.blocks;
     out->first_offset = host.first;
     return S3DG_OK;
+}
+
+}  // namespace s3dg
+
+extern "C" {
+
+static int verify_run(s3dg_ctx *c, const void *src, uint64_t obj_size, uint64_t stride, uint64_t n_objs,
+                      uint64_t blk_lo, uint64_t blk_hi, uint64_t seed_base, uint64_t first_obj,
+                      const PrefixParams &pp, hipStream_t s, s3dg_verify_result *out) {
+    return verify_with_record(c, s, "launch k_verify_stream", [&](VerifyRec *rec) {
+        return launch_verify_stream(cfg_for(c), (const uint8_t *)src, obj_size, stride, n_objs, (uint32_t)blk_lo,
+                                    (uint32_t)blk_hi, seed_base, first_obj, pp, c->base_dev, 0, rec, s);
+    }, out);
 }
 
 static void verify_clean(s3dg_verify_result *out) {

@@ -756,7 +756,9 @@ int host_run_split(HostStaging *sg0, const HostJob &J, uint8_t *buf, uint64_t po
 // Verify buf[0, n) (any alignment, read-only memory included) against the
 // job's object: 64 MiB chunks copied H2D into the staging set's two device
 // chunks on its two streams in turn (chunk k+1's copy overlaps chunk k's
-// kernel), each verified as a block range of the object.  The chunks add into
+// kernel), each verified as a block range of the object (4 KiB blocks through
+// k_verify_stream; a DG1 job's 1 MiB blocks, 64 per chunk, through
+// k_verify_keystream).  The chunks add into
 // one device record of the staging set, each launch offset by its chunk's
 // position in buf, so the record read back at the end holds the call's sums
 // and its lowest differing offset.
@@ -766,18 +768,26 @@ static int host_verify(HostStaging *sg, const HostJob &J, const uint8_t *buf, ui
     H_TRY(ds.err, "hipSetDevice");
     auto run = [&]() -> int {
         if (int r = upload_user_base(sg, J)) return r;
-        const void *base = base_for(S, sg, J);
+        const void *base = J.dgen ? nullptr : base_for(S, sg, J);
         if (!sg->vrec) H_TRY(hipMalloc((void **)&sg->vrec, sizeof(VerifyRec)), "hipMalloc(verify record)");
         H_TRY(verify_rec_reset(sg->vrec, sg->st[0]), "hipMemsetAsync(verify record)");
         H_TRY(hipStreamSynchronize(sg->st[0]), "hipStreamSynchronize");   // before the other stream adds to it
-        const uint64_t per = kChunk / kBlk, nb = (n + kBlk - 1) / kBlk;
+        // generation blocks: 4 KiB, or DG1's 1 MiB (64 per chunk)
+        const uint64_t gb = J.dgen ? kDgenBlock : (uint64_t)kBlk;
+        const uint64_t per = kChunk / gb, nb = (n + gb - 1) / gb;
         int k = 0;
         for (uint64_t pb = 0; pb < nb; pb += per, ++k) {
             const uint64_t pe = pb + per < nb ? pb + per : nb;
             const int sl = k & 1;
-            const uint64_t lo = pb * kBlk, hi = pe * kBlk < n ? pe * kBlk : n;
+            const uint64_t lo = pb * gb, hi = pe * gb < n ? pe * gb : n;
             H_TRY(hipMemcpyAsync(sg->buf[sl], buf + lo, hi - lo, hipMemcpyHostToDevice, sg->st[sl]),
                   "hipMemcpyAsync(H2D)");
+            if (J.dgen) {
+                if (int r = dgen_verify_launch(S->ctx, sg->buf[sl], J.obj_len, 0, 1, pb, pe, J.dedup, J.f_num, J.f_den,
+                                               J.entropy, 0, lo, sg->vrec, sg->st[sl]))
+                    return r;
+                continue;
+            }
             H_TRY(launch_verify_stream(ctx_stream_cfg(S->ctx), (const uint8_t *)sg->buf[sl], J.obj_len, 0, 1,
                                        (uint32_t)pb, (uint32_t)pe, J.entropy, 0, J.pp, base, lo, sg->vrec,
                                        sg->st[sl]),
@@ -964,6 +974,29 @@ int s3dlio_verify_controlled_data_seeded(const uint8_t *buf, size_t len, size_t 
     HostStaging *sg = nullptr;
     if (int r = host_staging_acquire(slot, &sg)) return r;
     const int r = host_verify(sg, J, buf, len, out);
+    host_staging_release(sg);
+    return r;
+}
+
+int s3dg_verify_generated_data(const uint8_t *buf, uint64_t size, uint64_t dedup, uint64_t compress, uint64_t seed,
+                               s3dg_verify_result *out) {
+    if (!out) return s3dg_internal_fail(S3DG_EINVAL, "null output");
+    out->mismatched_bytes = 0;
+    out->mismatched_blocks = 0;
+    out->first_offset = UINT64_MAX;
+    if (size == 0) return S3DG_OK;
+    if (!buf) return s3dg_internal_fail(S3DG_EINVAL, "null buffer");
+    HostJob J;   // the DG1 object of s3dg_gen_create(size, dedup, compress, 1, seed)
+    J.dgen = true;
+    J.obj_len = size;
+    J.entropy = seed;
+    J.dedup = dedup == 0 ? 1 : dedup;
+    if (int r = s3dg_compress_ratio(compress, &J.f_num, &J.f_den)) return r;
+    int slot = 0;
+    if (int r = host_next_slot(&slot)) return r;
+    HostStaging *sg = nullptr;
+    if (int r = host_staging_acquire(slot, &sg)) return r;
+    const int r = host_verify(sg, J, buf, size, out);
     host_staging_release(sg);
     return r;
 }

@@ -196,6 +196,15 @@ hipError_t launch_keystream(uint8_t *dst, const KeystreamArgs &A, const uint64_t
                            const uint64_t *tail_jtab = nullptr);
 hipError_t keystream_occupancy(const KsShape &sh, int *wgs_per_cu);
 
+// Verify (k_verify_keystream), the read-side twin of launch_keystream: the
+// bytes at src against the keystream of A (z0 = 0, lpc and span from
+// ks_verify_plan, so every lane region is whole 4 KiB granules; chunk_bytes a
+// multiple of 4096), on a static grid of 1-wave workgroups.  rec and off0 as
+// for launch_verify_stream: the caller zeroes rec on the stream first, the
+// launch adds to it, off0 is added to every reported offset.
+hipError_t launch_verify_keystream(const uint8_t *src, const KeystreamArgs &A, const uint64_t *jtab, uint64_t off0,
+                                   VerifyRec *rec, hipStream_t s);
+
 // thr/nthr: records for the tiled shape's trailing loads (lc.prefetch_tiles), or null
 hipError_t launch_write_ceiling(const LaunchCfg &lc, uint8_t *dst, uint64_t len,
                                 uint32_t pattern, const TileRec *thr, uint64_t nthr, hipStream_t s);
@@ -224,6 +233,13 @@ int fill_chunk(s3dg_ctx *c, void *dst, uint64_t obj_size, uint64_t stride, uint6
 int dgen_chunk(s3dg_ctx *c, void *dst, uint64_t obj_size, uint64_t stride, uint64_t n_objs, uint64_t blk_lo,
                uint64_t blk_hi, uint64_t dedup, uint32_t f_num, uint32_t f_den, uint64_t seed_base,
                uint64_t first_obj, void *stream);
+
+// The verify twin of dgen_chunk (k_verify_keystream): enqueues the compare of
+// the same blocks at src on `stream`, adding to rec (device; zeroed by the
+// caller on a stream ordered before); off0 is added to every reported offset.
+int dgen_verify_launch(s3dg_ctx *c, const void *src, uint64_t obj_size, uint64_t stride, uint64_t n_objs,
+                       uint64_t blk_lo, uint64_t blk_hi, uint64_t dedup, uint32_t f_num, uint32_t f_den,
+                       uint64_t seed_base, uint64_t first_obj, uint64_t off0, VerifyRec *rec, void *stream);
 
 // ---- object assembly (s3dg_object.cpp) ---------------------------------------
 void object_frame(int type, uint64_t elements, uint64_t len, uint32_t pcrc, std::vector<uint8_t> &pre,

@@ -749,9 +749,25 @@ __device__ __forceinline__ uint64_t ks_remap(const KeystreamArgs &A, uint64_t b)
 
 // One work unit: wave w of remapped workgroup bid, i.e. lanes
 // [(bid*W + w)*64, +64) of the launch.  myrows: this wave's LDS rows.
-template <int D, int W, int SP>
+//
+// V (k_verify_keystream): the read-side twin.  The unit derives the same
+// seeds, jumps, draws, tail draw and zero prefix into the same LDS rows, and
+// where the fill stores a row piece it compares the piece with `dst`'s bytes
+// instead; it stores nothing.  A stage's whole pieces (those that end at or
+// below their lane region's length) are loaded before the stage's draws, so
+// their latency hides behind the PRNG; the ragged piece of a chunk's or an
+// object's end is read byte by byte below that length only.  Lane regions of
+// a verify launch are whole 4 KiB granules (span % 512 == 0, chunks start on a
+// granule of their object), so a row's granule is 4096 / (8 D) consecutive
+// stages: `vmask` holds, per row, whether its current granule has shown a
+// difference (set from ballots, so it is wave-uniform), and its popcount is
+// added to the unit's granule count when the granule closes.  Only a unit that
+// found a difference touches rec, from lane 0: two 64-bit adds and a 64-bit
+// min (vector atomics); off0 is added to the reported offset.
+template <int D, int W, int SP, bool V = false>
 __device__ __forceinline__ void ks_unit(uint8_t *dst, const KeystreamArgs &A, const uint64_t *jtab,
-                                        uint8_t *myrows, uint32_t l, uint64_t bid, uint32_t w) {
+                                        uint8_t *myrows, uint32_t l, uint64_t bid, uint32_t w,
+                                        VerifyRec *rec = nullptr, uint64_t off0 = 0) {
     static_assert(D == 16 || D == 32 || D == 64, "draws per stage");
     constexpr int RS = D * 8 + 16;     // row stride: + 16 B pad, conflict-light ds_write_b128 rows
     constexpr int P = D / 2;           // 16-byte pieces per row
@@ -810,10 +826,103 @@ __device__ __forceinline__ void ks_unit(uint8_t *dst, const KeystreamArgs &A, co
     };
     const bool full_rows = __all(rlen == span * 8u);
 
+    // V: the stage's pieces of src (then src ^ expected), this lane's count
+    // and lowest offset, the rows' granule state and the unit's granule count
+    typedef u32x4 VStage[V ? P : 1];
+    VStage g;
+    uint64_t vcnt = 0, vfirst = ~0ull, vmask = 0;
+    uint32_t vblocks = 0;
+    auto v_load = [&](VStage &g, uint32_t it) {
+        const uint32_t o = it * (D * 8) + piece * 16;
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            g[i] = u32x4{0u, 0u, 0u, 0u};
+            // nontemporal, as k_verify_stream: the bytes are read once
+            if (full_rows || o + 16 <= rrem[i])
+                g[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(dst + raddr[i] + o));
+        }
+    };
+    // expected pieces: zeros (an all-zero wave) or the LDS rows
+    auto v_compare = [&](VStage &g, uint32_t it, bool zeros) {
+        const uint32_t o = it * (D * 8) + piece * 16;
+        uint32_t dm = 0;                                  // bit i: this lane's piece of row group i differs
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            u32x4 e = {0u, 0u, 0u, 0u};
+            if (!zeros) e = *reinterpret_cast<const u32x4 *>(myrows + (R * i + l / P) * RS + piece * 16);
+            if (full_rows || o + 16 <= rrem[i]) {
+                g[i] ^= e;
+            } else if (o < rrem[i]) {                     // ragged end: the nb < 16 bytes below the region's length
+                const uint32_t nb = rrem[i] - o;
+                const uint8_t *p = dst + raddr[i] + o;
+                uint64_t lo = 0, hi = 0;
+                for (uint32_t b = 0; b < nb; ++b) {
+                    const uint64_t v = p[b];
+                    if (b < 8) lo |= v << (8 * b);
+                    else hi |= v << (8 * (b - 8));
+                }
+                const uint64_t mlo = nb >= 8 ? ~0ull : ~(~0ull << (8 * nb));
+                const uint64_t mhi = nb <= 8 ? 0ull : ~(~0ull << (8 * (nb - 8)));
+                lo = (lo ^ (((uint64_t)e.y << 32) | e.x)) & mlo;
+                hi = (hi ^ (((uint64_t)e.w << 32) | e.z)) & mhi;
+                g[i] = u32x4{(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
+            }
+            if (g[i].x | g[i].y | g[i].z | g[i].w) dm |= 1u << i;
+        }
+        if (__any(dm != 0)) {                             // the clean path ends here: one vote per stage
+#pragma unroll
+            for (int i = 0; i < P; ++i) {
+                const bool d = (dm >> i) & 1u;
+                const uint64_t bal = __ballot(d);         // lanes [j P, (j+1) P): row R i + j
+                if (bal == 0) continue;
+#pragma unroll
+                for (int j = 0; j < R; ++j)
+                    if ((bal >> (j * P)) & (~0ull >> (64 - P))) vmask |= 1ull << (R * i + j);
+                if (d) {
+                    uint32_t c = 0, f = 16;
+                    diff_piece(g[i], 0, c, f);
+                    vcnt += c;
+                    const uint64_t pos = off0 + raddr[i] + o + f;
+                    vfirst = pos < vfirst ? pos : vfirst;
+                }
+            }
+        }
+        constexpr uint32_t GS = kBlk / (D * 8);           // stages per 4 KiB granule of a row
+        if ((it + 1) % GS == 0 || it + 1 == iters) {
+            vblocks += (uint32_t)__builtin_popcountll(vmask);
+            vmask = 0;
+        }
+    };
+    auto v_finish = [&]() {
+        if (!__any(vcnt != 0)) return;                    // clean: no store, no atomic
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            vcnt += __shfl_xor(vcnt, d, 64);
+            const uint64_t f = __shfl_xor(vfirst, d, 64);
+            vfirst = f < vfirst ? f : vfirst;
+        }
+        if (l == 0) {
+            atomicAdd(reinterpret_cast<unsigned long long *>(&rec->bytes), (unsigned long long)vcnt);
+            atomicAdd(reinterpret_cast<unsigned long long *>(&rec->blocks), (unsigned long long)vblocks);
+            atomicMin(reinterpret_cast<unsigned long long *>(&rec->first), (unsigned long long)vfirst);
+        }
+    };
+
     // A wave whose regions all lie inside their chunks' zero prefixes (DG1,
     // compress > 1) stores zeros: no jump, no PRNG.
     if (__all(rlen == 0 || rb + rlen <= zlen)) {
         row_dest();
+        if constexpr (V) {
+            // compares against zeros, one stage of loads in flight: a second
+            // stage's 128 registers do not fit beside the row addresses (the
+            // compiler spills ~200 VGPRs to scratch)
+            for (uint32_t it = 0; it < iters; ++it) {
+                v_load(g, it);
+                v_compare(g, it, true);
+            }
+            v_finish();
+            return;
+        }
         const u32x4 z = {0u, 0u, 0u, 0u};
         for (uint32_t it = 0; it < iters; ++it) {
             const uint32_t o = it * (D * 8) + piece * 16;
@@ -894,6 +1003,7 @@ __device__ __forceinline__ void ks_unit(uint8_t *dst, const KeystreamArgs &A, co
     for (uint32_t it = 0; it < iters; ++it) {
         const uint64_t dg = d0 + (uint64_t)it * D;
         const bool plain = __all(it != it_tail);
+        if constexpr (V) v_load(g, it);   // in flight during the draws
         if (plain) {
 #pragma unroll
             for (int q = 0; q < D; q += 2) {
@@ -941,7 +1051,9 @@ __device__ __forceinline__ void ks_unit(uint8_t *dst, const KeystreamArgs &A, co
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const uint32_t o = it * (D * 8) + piece * 16;               // offset within the row's region
-        if (full_rows) {
+        if constexpr (V) {
+            v_compare(g, it, false);
+        } else if (full_rows) {
             // Pieces are read from LDS a group of 8 ahead of their stores, so
             // each read's latency hides behind the previous group's stores
             // (the compiler otherwise pairs each read with its store and waits
@@ -981,6 +1093,7 @@ __device__ __forceinline__ void ks_unit(uint8_t *dst, const KeystreamArgs &A, co
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
+    if constexpr (V) v_finish();
 #if S3DG_KS_TRACE
     if (l == 0 && g_ks_trace) {
         // bits 48-63: HW_ID's wave/SIMD/pipe/CU/SH/SE fields (start stamp),
@@ -1062,6 +1175,20 @@ __global__ __launch_bounds__(64 * W) void k_keystream(uint8_t *dst, KeystreamArg
         if (second) ks_unit<D, W, SP>(dst, A2, jtab2, myrows, l, ks_remap(A2, b), ww);
         else ks_unit<D, W, SP>(dst, A, jtab, myrows, l, ks_remap(A, b), ww);
     }
+}
+
+// Verify, the read-side twin of k_keystream: ks_unit's compare variant over a
+// static grid of 1-wave workgroups (workgroup b = lanes [64 b, 64 b + 64) of
+// the launch, dealing order), 64-draw stages.  A (z0 = 0, lane regions of
+// whole granules: ks_verify_plan) covers zero prefixes and tails in one launch.
+// No global store; rec is touched only by units that found a difference.
+template <int D>
+__global__ __launch_bounds__(64) void k_verify_keystream(const uint8_t *src, KeystreamArgs A, const uint64_t *jtab,
+                                                         uint64_t off0, VerifyRec *rec) {
+    constexpr int RS = D * 8 + 16;
+    __shared__ __attribute__((aligned(16))) uint8_t rows[64 * RS];
+    ks_unit<D, 1, kStorePlain, true>(const_cast<uint8_t *>(src), A, jtab, rows, threadIdx.x & 63, blockIdx.x, 0, rec,
+                                     off0);
 }
 
 // DG1 zero prefixes in the fill's store shape (paired with a keystream launch
@@ -1462,6 +1589,25 @@ hipError_t keystream_occupancy(const KsShape &sh, int *wgs_per_cu) {
     hipError_t e;
     S3DG_KS_DISPATCH(e, occ_ks_one, sh, lds, wgs_per_cu);
     return e;
+}
+
+hipError_t launch_verify_keystream(const uint8_t *src, const KeystreamArgs &A0, const uint64_t *jtab, uint64_t off0,
+                                   VerifyRec *rec, hipStream_t s) {
+    (void)hipGetLastError();
+    // z0 = 0, 64-draw stages, lane regions of whole granules
+    if (A0.z0 || A0.doff || A0.span == 0 || A0.span % (kBlk / 8) || (A0.chunk_bytes & (kBlk - 1)) ||
+        (A0.lpc & (A0.lpc - 1)) || A0.lpc == 0)
+        return hipErrorInvalidValue;
+    KeystreamArgs A = A0;
+    const uint64_t waves = (A.nchunks * A.lpc + 63) / 64;
+    if (waves == 0) return hipSuccess;
+    if (waves * 64 > 0xFFFFFFFFull) return hipErrorInvalidValue;   // 32-bit work-item counts (kMaxGridX)
+    A.xg = 1;
+    A.nwg = (uint32_t)waves;
+    A.ctr = nullptr;
+    A.par = 0;
+    hipLaunchKernelGGL((k_verify_keystream<64>), dim3((uint32_t)waves), dim3(64), 0, s, src, A, jtab, off0, rec);
+    return hipGetLastError();
 }
 
 hipError_t launch_zero_prefix(uint8_t *dst, uint64_t nchunks, uint64_t cpo, uint64_t obj_stride, uint64_t chunk_bytes,

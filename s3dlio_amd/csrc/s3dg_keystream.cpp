@@ -3,6 +3,7 @@
 // generator in 1 MiB blocks.
 #include "s3dg_ctx.h"
 #include "s3dg_jump.h"
+#include "s3dg_ks_verify_plan.h"
 
 using namespace s3dg;
 
@@ -142,8 +143,9 @@ namespace {
 
 // dgen_chunk's argument checks, for blocks [blk_lo, blk_hi) of an object of nb blocks.
 int dgen_check(const void *dst, uint64_t obj_size, uint64_t stride, uint64_t n_objs, uint64_t blk_lo, uint64_t blk_hi,
-               uint64_t nb, uint32_t f_num, uint32_t f_den) {
-    if (!dst || !aligned16(dst) || (stride & 15u)) return fail(S3DG_EINVAL, "dst and stride must be 16-byte aligned");
+               uint64_t nb, uint32_t f_num, uint32_t f_den, const char *ptr_name = "dst") {
+    if (!dst || !aligned16(dst) || (stride & 15u))
+        return fail(S3DG_EINVAL, std::string(ptr_name) + " and stride must be 16-byte aligned");
     const uint64_t span_bytes = (blk_hi * kDgenBlock < obj_size ? blk_hi * kDgenBlock : obj_size) - blk_lo * kDgenBlock;
     if (n_objs > 1 && stride < span_bytes) return fail(S3DG_EINVAL, "stride too small: objects overlap");
     if (f_den == 0 || f_num >= f_den) return fail(S3DG_EINVAL, "need f_num < f_den");
@@ -316,3 +318,139 @@ int dgen_chunk(s3dg_ctx *c, void *dst, uint64_t obj_size, uint64_t stride, uint6
 }
 
 }  // namespace s3dg
+
+// ---- verification (k_verify_keystream) -----------------------
+namespace {
+
+// The verify launch's own lane plan (ks_verify_plan: lane regions of whole
+// 4 KiB granules, z0 = 0) from the mode's min_lane_draws knob, and its jump
+// table from the context's cache.
+int ks_verify_lanes(s3dg_ctx *c, int mode, uint64_t chunk_bytes, uint64_t nchunks, bool zero_prefix,
+                    KeystreamArgs &A, const uint64_t **jtab) {
+    const uint64_t md = c->ks_min_draws[mode];
+    uint64_t knob = md == kDefaultKsMinDraws[mode] ? 0 : md;        // 0: not set by the caller
+    if (mode == 1 && zero_prefix && !knob) knob = kDgenPrefixMinDraws;   // as the fill: more all-zero waves
+    const KsVerifyPlan P = ks_verify_plan(chunk_bytes, nchunks, (uint32_t)c->cus, knob);
+    if (P.span > 0xFFFFFFFFull) return fail(S3DG_EINVAL, "chunk too large");
+    A.lpc = P.lpc;
+    A.span = (uint32_t)P.span;
+    A.z0 = 0;
+    return jump_table(c, P.lpc, P.span, 0, jtab);
+}
+
+void verify_clean(s3dg_verify_result *out) {
+    out->mismatched_bytes = 0;
+    out->mismatched_blocks = 0;
+    out->first_offset = UINT64_MAX;
+}
+
+}  // namespace
+
+namespace s3dg {
+
+int dgen_verify_launch(s3dg_ctx *c, const void *src, uint64_t obj_size, uint64_t stride, uint64_t n_objs,
+                       uint64_t blk_lo, uint64_t blk_hi, uint64_t dedup, uint32_t f_num, uint32_t f_den,
+                       uint64_t seed_base, uint64_t first_obj, uint64_t off0, VerifyRec *rec, void *stream) {
+    if (obj_size == 0 || n_objs == 0) return S3DG_OK;
+    const uint64_t nb = (obj_size + kDgenBlock - 1) / kDgenBlock;
+    if (blk_hi > nb) blk_hi = nb;
+    if (blk_lo >= blk_hi) return S3DG_OK;
+    if (int r = dgen_check(src, obj_size, stride, n_objs, blk_lo, blk_hi, nb, f_num, f_den, "src")) return r;
+    KeystreamArgs A{};
+    const uint64_t *jt = nullptr;
+    if (int r = ks_verify_lanes(c, 1, kDgenBlock, (blk_hi - blk_lo) * n_objs, f_num > 0, A, &jt)) return r;
+    const uint64_t U = s3dg_unique_blocks(nb, dedup);
+    A.cpo = blk_hi - blk_lo;
+    A.nchunks = A.cpo * n_objs;
+    A.chunk_bytes = kDgenBlock;
+    A.obj_len = obj_size;
+    A.chunk0 = blk_lo;
+    A.obj_stride = stride;
+    A.seed_base = seed_base + (first_obj << 32);
+    A.seed_step = 1ull << 32;
+    A.seed_mode = 1;
+    A.unique = U == nb ? 0xFFFFFFFFu : (uint32_t)U;
+    A.m_unique = fastmod_magic(U == nb ? 1u : (uint32_t)U);
+    A.zf_num = f_num;
+    A.zf_den = f_den;
+    HIP_TRY(launch_verify_keystream((const uint8_t *)src, A, jt, off0, rec, (hipStream_t)stream),
+            "launch k_verify_keystream(dgen)");
+    return S3DG_OK;
+}
+
+}  // namespace s3dg
+
+namespace {
+
+// A device verify call over DG1 objects: the launch's argument errors come
+// back as they are (with their text), HIP errors through the record handling.
+int dgen_verify(s3dg_ctx *c, const void *src, uint64_t obj_size, uint64_t stride, uint64_t n_objs, uint64_t blk_lo,
+                uint64_t blk_hi, uint64_t dedup, uint32_t f_num, uint32_t f_den, uint64_t seed_base,
+                uint64_t first_obj, void *stream, s3dg_verify_result *out) {
+    CTX_SCOPE(c);
+    if (!out) return fail(S3DG_EINVAL, "null output");
+    verify_clean(out);
+    if (obj_size == 0 || n_objs == 0) return S3DG_OK;
+    const uint64_t nb = (obj_size + kDgenBlock - 1) / kDgenBlock;
+    if (blk_hi > nb) blk_hi = nb;
+    if (blk_lo >= blk_hi) return S3DG_OK;
+    if (int r = dgen_check(src, obj_size, stride, n_objs, blk_lo, blk_hi, nb, f_num, f_den, "src")) return r;
+    int lr = S3DG_OK;
+    std::string lmsg;
+    const int r = verify_with_record(c, (hipStream_t)stream, "launch k_verify_keystream(dgen)", [&](VerifyRec *rec) {
+        lr = dgen_verify_launch(c, src, obj_size, stride, n_objs, blk_lo, blk_hi, dedup, f_num, f_den, seed_base,
+                                first_obj, 0, rec, stream);
+        if (lr != S3DG_OK) lmsg = s3dg_last_error();
+        return lr == S3DG_OK ? hipSuccess : hipErrorInvalidValue;
+    }, out);
+    return lr != S3DG_OK ? fail(lr, lmsg) : r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int s3dg_verify_xoshiro(s3dg_ctx *c, const void *src, uint64_t len, uint64_t chunk_bytes, uint64_t seed_base,
+                        void *stream, s3dg_verify_result *out) {
+    CTX_SCOPE(c);
+    if (!out) return fail(S3DG_EINVAL, "null output");
+    verify_clean(out);
+    if (len == 0) return S3DG_OK;
+    if (chunk_bytes == 0 || (chunk_bytes & (kBlk - 1)))
+        return fail(S3DG_EINVAL, "chunk_bytes must be a positive multiple of 4096 (the verify's 4 KiB granules; "
+                                 "s3dg_xoshiro_fill itself takes multiples of 128)");
+    if (!src || !aligned16(src)) return fail(S3DG_EINVAL, "src must be a 16-byte aligned device pointer");
+    const uint64_t nchunks = (len + chunk_bytes - 1) / chunk_bytes;
+    KeystreamArgs A{};
+    const uint64_t *jt = nullptr;
+    if (int r = ks_verify_lanes(c, 0, chunk_bytes, nchunks, false, A, &jt)) return r;
+    A.nchunks = nchunks;
+    A.chunk_bytes = chunk_bytes;
+    A.obj_len = len;
+    A.chunk0 = 0;
+    A.seed_base = seed_base;
+    A.seed_mode = 0;
+    A.unique = 0xFFFFFFFFu;
+    A.m_unique = 0;
+    A.zf_num = 0;
+    A.zf_den = 1;
+    return verify_with_record(c, (hipStream_t)stream, "launch k_verify_keystream", [&](VerifyRec *rec) {
+        return launch_verify_keystream((const uint8_t *)src, A, jt, 0, rec, (hipStream_t)stream);
+    }, out);
+}
+
+int s3dg_verify_dgen(s3dg_ctx *c, const void *src, uint64_t obj_size, uint64_t blk_lo, uint64_t blk_hi,
+                     uint64_t dedup, uint32_t f_num, uint32_t f_den, uint64_t seed, void *stream,
+                     s3dg_verify_result *out) {
+    return dgen_verify(c, src, obj_size, 0, 1, blk_lo, blk_hi, dedup, f_num, f_den, seed, 0, stream, out);
+}
+
+int s3dg_verify_dgen_stream(s3dg_ctx *c, const void *src, uint64_t obj_size, uint64_t stride, uint64_t n_objs,
+                            uint64_t dedup, uint32_t f_num, uint32_t f_den, uint64_t seed_base, uint64_t first_obj,
+                            void *stream, s3dg_verify_result *out) {
+    if (n_objs > 1 && stride < obj_size) return fail(S3DG_EINVAL, "stride < obj_size: objects overlap");
+    return dgen_verify(c, src, obj_size, stride, n_objs, 0, ~0ull, dedup, f_num, f_den, seed_base, first_obj, stream,
+                       out);
+}
+
+}  // extern "C"

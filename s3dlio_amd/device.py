@@ -406,6 +406,47 @@ class Context:
         call("s3dg_dgen_fill_stream", self._h, self._dst(dst, need), int(obj_size), int(stride), int(n_objs),
              int(dedup), fn, fd, int(seed_base) & (2**64 - 1), int(first_obj), self._s(stream))
 
+    # -- keystream verification (synchronous on `stream`) -------------------------
+    # The read-side twins of xoshiro_fill / dgen_fill / dgen_fill_stream: the
+    # GPU regenerates each chunk's keystream and compares it with the tensor's
+    # bytes, writing nothing.  Same arguments, same bounds check; blocks in the
+    # result are 4 KiB granules within each object.
+    def verify_xoshiro(self, src, nbytes: int | None = None, chunk_bytes: int = 2 << 20,
+                       seed_base: int = 0, stream=None) -> VerifyResult:
+        """Compare `nbytes` at src with xoshiro_fill's bytes for the same arguments;
+        chunk_bytes must be a positive multiple of 4096."""
+        n = _nbytes(src) if nbytes is None else int(nbytes)
+        r = _lib.VerifyRec()
+        call("s3dg_verify_xoshiro", self._h, self._src(src, n), n, int(chunk_bytes),
+             int(seed_base) & (2**64 - 1), self._s(stream), ctypes.byref(r))
+        return VerifyResult._of(r)
+
+    def verify_dgen(self, src, obj_size: int, blk_lo: int = 0, blk_hi: int | None = None,
+                    dedup: int = 1, compress=1, seed: int = 0, stream=None) -> VerifyResult:
+        """DG1 blocks [blk_lo, blk_hi) of an obj_size-byte object (1 MiB blocks),
+        block blk_lo at src; first_offset counts from src."""
+        fn, fd = compress_ratio(compress)
+        hi = (obj_size + (1 << 20) - 1) >> 20 if blk_hi is None else blk_hi
+        need = max(0, min(int(hi) << 20, int(obj_size)) - (int(blk_lo) << 20))
+        r = _lib.VerifyRec()
+        call("s3dg_verify_dgen", self._h, self._src(src, need), int(obj_size), int(blk_lo), int(hi),
+             int(dedup), fn, fd, int(seed) & (2**64 - 1), self._s(stream), ctypes.byref(r))
+        return VerifyResult._of(r)
+
+    def verify_dgen_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None,
+                           dedup: int = 1, compress=1, seed_base: int = 0, first_obj: int = 0,
+                           stream=None) -> VerifyResult:
+        """n_objs DG1 objects as dgen_fill_stream lays them out; counts are summed
+        over the objects, first_offset counts from src (stride gaps included,
+        which are never read)."""
+        stride = obj_size if stride is None else stride
+        need = (int(n_objs) - 1) * int(stride) + int(obj_size) if n_objs > 0 and obj_size > 0 else 0
+        fn, fd = compress_ratio(compress)
+        r = _lib.VerifyRec()
+        call("s3dg_verify_dgen_stream", self._h, self._src(src, need), int(obj_size), int(stride), int(n_objs),
+             int(dedup), fn, fd, int(seed_base) & (2**64 - 1), int(first_obj), self._s(stream), ctypes.byref(r))
+        return VerifyResult._of(r)
+
     def write_ceiling(self, dst, nbytes: int | None = None, pattern: int = 0xA5A5A5A5,
                       stream=None) -> None:
         n = _nbytes(dst) if nbytes is None else int(nbytes)
