@@ -314,6 +314,71 @@ int s3dg_verify_dgen_stream(s3dg_ctx *ctx, const void *src, uint64_t obj_size, u
                             uint64_t seed_base, uint64_t first_obj, void *stream,
                             s3dg_verify_result *out);
 
+/* ---- measurement (read-only) ------------------------------
+ * What a payload is worth to a store that deduplicates and compresses at
+ * `block_bytes`: how many of its blocks are distinct and how many of its bytes
+ * are zero, the two ratios the reference's own tests compute on the CPU with a
+ * HashSet of blocks (tests/test_data-gen.rs:84-215).  No seed is needed, so
+ * unseeded output and data read back from a store can be measured too.
+ *
+ * Each object is cut into blocks of block_bytes from its own start; an
+ * object's last block may be ragged, and a ragged block never equals a full
+ * one (bytes and length are compared, as a HashSet<Vec<u8>> would).  Blocks
+ * are compared through 128-bit fingerprints: unique_blocks is the exact
+ * number of distinct fingerprints, and two different blocks share one with
+ * probability about 2^-64 per pair for data that was not built against the
+ * (public, fixed) keys.
+ *
+ * A handle accumulates: every add on any stream adds to one result, so data
+ * that passes through a ring in several launches or arrives in chunks is
+ * measured as one payload.  block_bytes: a positive multiple of 4096, at most
+ * 2^30.  flags: 0 or S3DG_MEASURE_HIST (a byte histogram, a second read of
+ * the same bytes).  Device memory per measured block: a 16-byte fingerprint
+ * in an array that grows by doubling, plus, while s3dg_measure_get runs, a
+ * 32-byte sort copy and hipCUB's radix-sort scratch (about 16 bytes more);
+ * per add and stream, 20 bytes per 4 KiB of the add as scratch.  Growing the
+ * array waits for the adds the handle has enqueued, on all their streams.
+ * The read pass runs 1, 2 or 4 wave64s per 4 KiB after
+ * s3dg_set_waves_per_block (auto: 1); results are identical.
+ * Destroy a handle before its context. */
+enum { S3DG_MEASURE_HIST = 1 };
+typedef struct s3dg_measure s3dg_measure;
+typedef struct {
+    uint64_t bytes;          /* payload bytes measured (stride gaps excluded) */
+    uint64_t zero_bytes;
+    uint64_t blocks;         /* blocks measured, ragged last blocks included */
+    uint64_t unique_blocks;  /* distinct among them (bytes and length) */
+    uint64_t hist[256];      /* byte histogram; all 0 without S3DG_MEASURE_HIST */
+} s3dg_measure_result;
+int s3dg_measure_create(s3dg_ctx *ctx, uint64_t block_bytes, int flags, s3dg_measure **out);
+int s3dg_measure_destroy(s3dg_measure *m);
+int s3dg_measure_reset(s3dg_measure *m);   /* waits for the enqueued adds; an empty handle again */
+/* n_objs objects of obj_size bytes at src + j*stride (device memory; src and
+ * stride 16-byte aligned, stride >= obj_size: the refusals of
+ * s3dg_verify_controlled_stream).  Asynchronous on `stream` and ordered like a
+ * fill: a later launch on the same stream may overwrite src.  Stride gaps and
+ * whatever follows the last object are never read.  Fingerprint slots are
+ * reserved on the host at call time, so adds from several threads on several
+ * streams are safe.  A zero-length add launches nothing. */
+int s3dg_measure_add_stream(s3dg_measure *m, const void *src, uint64_t obj_size, uint64_t stride,
+                            uint64_t n_objs, void *stream);
+/* Blocks [blk_lo, blk_hi) of one obj_size-byte object, in units of
+ * block_bytes, block blk_lo at src (blk_hi is clipped to the object): one
+ * large object passing through a smaller buffer. */
+int s3dg_measure_add_range(s3dg_measure *m, const void *src, uint64_t obj_size,
+                           uint64_t blk_lo, uint64_t blk_hi, void *stream);
+/* Waits for the enqueued adds, counts the distinct fingerprints on a copy
+ * and fills *out.  The handle is unchanged: get again, or add and get.  An
+ * empty handle yields all zeros. */
+int s3dg_measure_get(s3dg_measure *m, s3dg_measure_result *out);
+/* A host buffer (any alignment, read-only memory included) as one object,
+ * on a host slot's GPU: copied in chunks of whole blocks (up to 64 MiB; one
+ * block per chunk, in two buffers of the call's own, when block_bytes is
+ * larger) on the slot's two streams, each chunk an s3dg_measure_add_range.
+ * len == 0: all zeros, no GPU needed. */
+int s3dg_measure_data(const uint8_t *buf, uint64_t len, uint64_t block_bytes, int flags,
+                      s3dg_measure_result *out);
+
 /* ---- memory / copy helpers ------------------------------------------------ */
 int s3dg_device_alloc(s3dg_ctx *ctx, uint64_t bytes, void **out);
 int s3dg_device_free(s3dg_ctx *ctx, void *p);

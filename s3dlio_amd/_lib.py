@@ -53,6 +53,12 @@ class VerifyRec(ctypes.Structure):
     _fields_ = [("mismatched_bytes", c_u64), ("mismatched_blocks", c_u64), ("first_offset", c_u64)]
 
 
+class MeasureRec(ctypes.Structure):
+    """s3dg_measure_result"""
+    _fields_ = [("bytes", c_u64), ("zero_bytes", c_u64), ("blocks", c_u64), ("unique_blocks", c_u64),
+                ("hist", c_u64 * 256)]
+
+
 # name -> (restype, argtypes); the exact export list of include/s3dlio_gpu.h
 SIGNATURES = {
     "s3dg_ctx_create": (c_int, [c_int, ctypes.POINTER(c_vp)]),
@@ -102,6 +108,13 @@ SIGNATURES = {
                                  ctypes.POINTER(VerifyRec)]),
     "s3dg_verify_dgen_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_u64, c_u32, c_u32, c_u64, c_u64, c_vp,
                                         ctypes.POINTER(VerifyRec)]),
+    "s3dg_measure_create": (c_int, [c_vp, c_u64, c_int, ctypes.POINTER(c_vp)]),
+    "s3dg_measure_destroy": (c_int, [c_vp]),
+    "s3dg_measure_reset": (c_int, [c_vp]),
+    "s3dg_measure_add_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp]),
+    "s3dg_measure_add_range": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp]),
+    "s3dg_measure_get": (c_int, [c_vp, ctypes.POINTER(MeasureRec)]),
+    "s3dg_measure_data": (c_int, [c_vp, c_u64, c_u64, c_int, ctypes.POINTER(MeasureRec)]),
     "s3dg_write_ceiling": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
     "s3dg_write_ceiling_tiled": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
     "s3dg_write_ceiling_fill": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),

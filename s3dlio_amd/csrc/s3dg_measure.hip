@@ -1,0 +1,435 @@
+// s3dg_measure.hip — read-only analysis of a payload: a
+// 128-bit fingerprint per block of block_bytes and the zero-byte count
+// (k_measure per 4 KiB granule, k_measure_blocks per block), the exact number
+// of distinct fingerprints (two stable hipCUB radix sorts on a copy, then
+// k_count_distinct), and an optional byte histogram (k_byte_hist).  Nothing
+// here writes the measured buffer; results leave through plain vector stores
+// and vector atomics.
+#include <hipcub/hipcub.hpp>
+
+#include "s3dg_measure.h"
+
+namespace s3dg {
+namespace {
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+constexpr uint32_t kGran = (uint32_t)kMeasureGranule;
+
+// ---- the fingerprint ----------------------------------------------------------
+// A block is a sequence of 16-byte pieces, piece p at byte 16 p of the block
+// (the ragged last piece zero-padded).  Each piece adds one term to each of
+// two 64-bit sums, all adds wrapping:
+//   x       = mix32(p + 0x9E3779B9)                         (a bijection of p)
+//   k0 | k1<<32 = x * 0x9E3779B1 + 0x243F6A8885A308D3
+//   k2 | k3<<32 = x * 0x85EBCA77 + 0x13198A2E03707344
+//   k4 = rotl(k1,16) ^ k2   k5 = rotl(k3,16) ^ k0   k6 = rotl(k0,8) + k3   k7 = rotl(k2,24) + k1
+//   sum0 += (d0+k0)*(d1+k1) + (d2+k2)*(d3+k3)               (32-bit adds, 32x32 -> 64 products)
+//   sum1 += (d0+k4)*(d2+k5) + (d1+k6)*(d3+k7)
+// (the NH construction of UMAC with per-piece, per-dword keys, in two
+// pairings).  Sums commute, so lanes, waves and granules reduce in any order.
+// fp_final folds in the block's byte length and avalanches.
+__device__ __forceinline__ uint32_t rotl32(uint32_t v, int r) { return (v << r) | (v >> (32 - r)); }
+
+__device__ __forceinline__ void fp_piece(uint32_t p, u32x4 d, uint64_t &s0, uint64_t &s1) {
+    uint32_t x = p + 0x9E3779B9u;
+    x ^= x >> 16;
+    x *= 0x7FEB352Du;
+    x ^= x >> 15;
+    x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    const uint64_t a = (uint64_t)x * 0x9E3779B1u + 0x243F6A8885A308D3ull;
+    const uint64_t b = (uint64_t)x * 0x85EBCA77u + 0x13198A2E03707344ull;
+    const uint32_t k0 = (uint32_t)a, k1 = (uint32_t)(a >> 32), k2 = (uint32_t)b, k3 = (uint32_t)(b >> 32);
+    const uint32_t k4 = rotl32(k1, 16) ^ k2, k5 = rotl32(k3, 16) ^ k0;
+    const uint32_t k6 = rotl32(k0, 8) + k3, k7 = rotl32(k2, 24) + k1;
+    s0 += (uint64_t)(d.x + k0) * (uint64_t)(d.y + k1);
+    s0 += (uint64_t)(d.z + k2) * (uint64_t)(d.w + k3);
+    s1 += (uint64_t)(d.x + k4) * (uint64_t)(d.z + k5);
+    s1 += (uint64_t)(d.y + k6) * (uint64_t)(d.w + k7);
+}
+
+__device__ __forceinline__ uint64_t fmix64(uint64_t h) {   // MurmurHash3's finaliser (a bijection)
+    h ^= h >> 33;
+    h *= 0xFF51AFD7ED558CCDull;
+    h ^= h >> 33;
+    h *= 0xC4CEB9FE1A85EC53ull;
+    h ^= h >> 33;
+    return h;
+}
+
+// For a fixed length a bijection of (s0, s1); the length separates a ragged
+// block from a full one that starts with the same bytes.
+__device__ __forceinline__ MeasureFp fp_final(uint64_t s0, uint64_t s1, uint64_t len) {
+    uint64_t a = fmix64(s0 + len * 0x9E3779B97F4A7C15ull);
+    const uint64_t b = fmix64((s1 + len * 0xD6E8FEB86659FD93ull) ^ a);
+    a += b;
+    return MeasureFp{a, b};
+}
+
+// 0x80 in every zero byte of x, exactly
+__device__ __forceinline__ uint32_t zero_bytes(uint32_t x) {
+    const uint32_t t = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
+    return (uint32_t)__builtin_popcount(~(t | x | 0x7F7F7F7Fu));
+}
+
+// Wave-wide sums without LDS traffic: a butterfly inside each row of 16 lanes
+// on the VALU's DPP operand path (xor 1, xor 2, then the half-row and row
+// mirrors, which add the other half's identical sums), and the four row sums
+// read into scalars.  Every lane must be active.  With shuffles (ds_bpermute,
+// 30 per wave for two 64-bit sums and a count) the reduction bounded the
+// kernel: 4850 GB/s at 2 waves per granule against 6300 at 1.
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+}
+template <int CTRL>
+__device__ __forceinline__ uint64_t dpp64(uint64_t v) {
+    return (uint64_t)dpp32<CTRL>((uint32_t)v) | ((uint64_t)dpp32<CTRL>((uint32_t)(v >> 32)) << 32);
+}
+__device__ __forceinline__ uint32_t rows32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
+           (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+}
+__device__ __forceinline__ uint64_t rows64(uint64_t v) {
+    uint64_t s = 0;
+#pragma unroll
+    for (int l = 0; l < 64; l += 16)
+        s += (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l) |
+             ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32);
+    return s;
+}
+__device__ __forceinline__ void wave_sums(uint64_t &s0, uint64_t &s1, uint32_t &z) {
+    constexpr int kXor1 = 0xB1, kXor2 = 0x4E, kHalfMirror = 0x141, kMirror = 0x140;   // quad_perm [1,0,3,2], [2,3,0,1]
+    s0 += dpp64<kXor1>(s0); s1 += dpp64<kXor1>(s1); z += dpp32<kXor1>(z);
+    s0 += dpp64<kXor2>(s0); s1 += dpp64<kXor2>(s1); z += dpp32<kXor2>(z);
+    s0 += dpp64<kHalfMirror>(s0); s1 += dpp64<kHalfMirror>(s1); z += dpp32<kHalfMirror>(z);
+    s0 += dpp64<kMirror>(s0); s1 += dpp64<kMirror>(s1); z += dpp32<kMirror>(z);
+    s0 = rows64(s0);
+    s1 = rows64(s1);
+    z = rows32(z);
+}
+
+__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int d) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, d, 64), hi = __shfl_xor((uint32_t)(v >> 32), d, 64);
+    return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+
+// The ragged piece of an object's end, bytes below L only, zero-padded; its
+// zero bytes among them are added to z.
+__device__ __forceinline__ u32x4 load_ragged(const uint8_t *bs, uint32_t o, uint32_t L, uint32_t &z) {
+    uint32_t dw[4] = {0u, 0u, 0u, 0u};
+    for (uint32_t b = 0; o + b < L; ++b) {
+        const uint32_t v = bs[o + b];
+        z += v == 0;
+        dw[b >> 2] |= v << (8 * (b & 3));
+    }
+    return u32x4{dw[0], dw[1], dw[2], dw[3]};
+}
+
+// ---- pass 1 -------------------------------------------------------------------
+// blockIdx.x = 4 KiB granule gran0 + x of the object range, blockIdx.y = object
+// (src already advanced to the sub-launch's first object; rec_base its first
+// record).  The reading rules are k_verify_stream's: a 16-byte piece is loaded
+// whole (nontemporal, the bytes are read once) only when it ends at or below
+// the range's length, the ragged piece byte by byte below it, nothing else.
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void k_measure(const uint8_t *src, uint64_t stride, uint64_t len,
+                                                     uint32_t gran0, uint32_t gpb, uint64_t gpo,
+                                                     uint64_t rec_base, MeasureFp *rfp, uint32_t *rz) {
+    constexpr int T = 64 * NW, SPL = 4 / NW;
+    __shared__ uint64_t w0[NW], w1[NW];
+    __shared__ uint32_t wz[NW];
+    const uint32_t t = threadIdx.x;
+    const uint32_t lane = t & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const uint32_t g = gran0 + blockIdx.x;
+    const uint8_t *bs = src + (uint64_t)blockIdx.y * stride + (uint64_t)g * kGran;
+    const uint64_t left = len - (uint64_t)g * kGran;              // the launcher keeps g * 4 KiB < len
+    const uint32_t L = left < kGran ? (uint32_t)left : kGran;
+    u32x4 G[SPL];
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+        const uint32_t o = (t + k * T) * 16;
+        G[k] = u32x4{0u, 0u, 0u, 0u};
+        if (o + 16 <= L) G[k] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(bs + o));
+    }
+    const uint32_t p0 = (g % gpb) * (kGran / 16);                 // the granule's first piece within its block
+    uint64_t s0 = 0, s1 = 0;
+    uint32_t z = 0;
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+        const uint32_t o = (t + k * T) * 16;
+        if (o >= L) continue;
+        u32x4 d = G[k];
+        if (o + 16 <= L) z += zero_bytes(d.x) + zero_bytes(d.y) + zero_bytes(d.z) + zero_bytes(d.w);
+        else d = load_ragged(bs, o, L, z);
+        fp_piece(p0 + (o >> 4), d, s0, s1);
+    }
+    wave_sums(s0, s1, z);   // all 64 lanes are active here
+    if constexpr (NW > 1) {
+        if (lane == 0) { w0[wave] = s0; w1[wave] = s1; wz[wave] = z; }
+        __syncthreads();
+        if (t == 0) {
+#pragma unroll
+            for (int w = 1; w < NW; ++w) { s0 += w0[w]; s1 += w1[w]; z += wz[w]; }
+        }
+    }
+    if (t == 0) {
+        const uint64_t r = rec_base + (uint64_t)blockIdx.y * gpo + g;
+        rfp[r] = MeasureFp{s0, s1};
+        rz[r] = z;
+    }
+}
+
+// ---- pass 2 -------------------------------------------------------------------
+// The workgroup's zero counts (one per thread) summed and added to *total:
+// one vector atomic per workgroup, none when the sum is zero.
+__device__ __forceinline__ void add_zero_total(uint64_t z, uint64_t *total) {
+    __shared__ uint64_t wsum[4];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) z += shfl_xor64(z, d);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = z;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint64_t s = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (s) atomicAdd(reinterpret_cast<unsigned long long *>(total), (unsigned long long)s);
+    }
+}
+
+// Block i of the add (object i / bpo, its block i % bpo): first record, granules, byte length.
+__device__ __forceinline__ void block_of(uint64_t i, uint64_t bpo, uint64_t gpo, uint32_t gpb, uint64_t block_bytes,
+                                         uint64_t last_block, uint64_t &r0, uint32_t &ng, uint64_t &blen) {
+    const uint64_t j = i / bpo, b = i - j * bpo;
+    r0 = j * gpo + b * gpb;
+    blen = b + 1 == bpo ? last_block : block_bytes;
+    ng = (uint32_t)((blen + kGran - 1) / kGran);
+}
+
+// One thread per block (blocks of a few granules).
+__global__ __launch_bounds__(256) void k_measure_blocks(const MeasureFp *rfp, const uint32_t *rz, uint64_t nblocks,
+                                                        uint64_t bpo, uint64_t gpo, uint32_t gpb,
+                                                        uint64_t block_bytes, uint64_t last_block, MeasureFp *fp,
+                                                        uint64_t *zero_total) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    uint64_t z = 0;
+    if (i < nblocks) {
+        uint64_t r0, blen, s0 = 0, s1 = 0;
+        uint32_t ng;
+        block_of(i, bpo, gpo, gpb, block_bytes, last_block, r0, ng, blen);
+        for (uint32_t k = 0; k < ng; ++k) {
+            const MeasureFp q = rfp[r0 + k];
+            s0 += q.lo;
+            s1 += q.hi;
+            z += rz[r0 + k];
+        }
+        fp[i] = fp_final(s0, s1, blen);
+    }
+    add_zero_total(z, zero_total);
+}
+
+// One wave per block (blocks of many granules), four blocks per workgroup.
+__global__ __launch_bounds__(256) void k_measure_blocks_wave(const MeasureFp *rfp, const uint32_t *rz,
+                                                             uint64_t nblocks, uint64_t bpo, uint64_t gpo,
+                                                             uint32_t gpb, uint64_t block_bytes, uint64_t last_block,
+                                                             MeasureFp *fp, uint64_t *zero_total) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    uint64_t z = 0;
+    if (i < nblocks) {
+        uint64_t r0, blen, s0 = 0, s1 = 0;
+        uint32_t ng;
+        block_of(i, bpo, gpo, gpb, block_bytes, last_block, r0, ng, blen);
+        for (uint32_t k = lane; k < ng; k += 64) {
+            const MeasureFp q = rfp[r0 + k];
+            s0 += q.lo;
+            s1 += q.hi;
+            z += rz[r0 + k];
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            s0 += shfl_xor64(s0, d);
+            s1 += shfl_xor64(s1, d);
+        }
+        if (lane == 0) fp[i] = fp_final(s0, s1, blen);
+    }
+    add_zero_total(z, zero_total);
+}
+
+// ---- distinct count -------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_fp_split(const MeasureFp *fp, uint64_t n, uint64_t *lo, uint64_t *hi) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const MeasureFp q = fp[i];
+        lo[i] = q.lo;
+        hi[i] = q.hi;
+    }
+}
+
+// Sorted (hi, lo): positions that differ from their predecessor.
+__global__ __launch_bounds__(256) void k_count_distinct(const uint64_t *lo, const uint64_t *hi, uint64_t n,
+                                                        uint64_t *distinct) {
+    uint64_t c = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
+        c += i == 0 || lo[i] != lo[i - 1] || hi[i] != hi[i - 1];
+    add_zero_total(c, distinct);
+}
+
+// ---- byte histogram ---------------------------------------------------------------
+// A grid sized to the chip; each workgroup walks granules r = blockIdx.x,
+// + gridDim.x, ... (granule r % gpo of object r / gpo), one 16-byte piece per
+// thread, under pass 1's reading rules.  Zero bytes are counted in registers
+// (half of a compress-2 payload: every lane would meet on one LDS word); the
+// other values go to the wave's own 256 LDS counters.  One flush per workgroup
+// into its slot of `part`, plain stores.
+__global__ __launch_bounds__(256) void k_byte_hist(const uint8_t *src, uint64_t stride, uint64_t len, uint64_t gpo,
+                                                   uint64_t total, uint32_t *part) {
+    __shared__ uint32_t cnt[4][256];
+    const uint32_t t = threadIdx.x, wave = t >> 6;
+    for (int w = 0; w < 4; ++w) cnt[w][t] = 0;
+    __syncthreads();
+    uint32_t z = 0;
+    const uint32_t o = t * 16;
+    for (uint64_t r = blockIdx.x; r < total; r += gridDim.x) {
+        const uint64_t j = r / gpo, g = r - j * gpo;
+        const uint8_t *bs = src + j * stride + g * kGran;
+        const uint64_t left = len - g * kGran;
+        const uint32_t L = left < kGran ? (uint32_t)left : kGran;
+        if (o + 16 <= L) {
+            const u32x4 d = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(bs + o));
+            const uint32_t dw[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                z += zero_bytes(dw[q]);
+                if (dw[q] == 0) continue;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const uint32_t v = (dw[q] >> (8 * b)) & 0xFFu;
+                    if (v) atomicAdd(&cnt[wave][v], 1u);
+                }
+            }
+        } else {
+            for (uint32_t b = 0; o + b < L; ++b) {
+                const uint32_t v = bs[o + b];
+                if (v) atomicAdd(&cnt[wave][v], 1u);
+                else ++z;
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) z += __shfl_xor(z, d, 64);
+    if ((t & 63) == 0) cnt[wave][0] = z;
+    __syncthreads();
+    part[(uint64_t)blockIdx.x * 256 + t] = cnt[0][t] + cnt[1][t] + cnt[2][t] + cnt[3][t];
+}
+
+// hist[b] += the workgroups' counts of value b (one thread per value).
+__global__ __launch_bounds__(256) void k_hist_reduce(const uint32_t *part, uint32_t nwg, uint64_t *hist) {
+    uint64_t s = 0;
+    for (uint32_t w = 0; w < nwg; ++w) s += part[(uint64_t)w * 256 + threadIdx.x];
+    if (s) atomicAdd(reinterpret_cast<unsigned long long *>(&hist[threadIdx.x]), (unsigned long long)s);
+}
+
+// A workgroup of k_byte_hist counts at most 2^19 granules (2^31 bytes) in its
+// 32-bit counters.  The grid is 8 workgroups per CU, so one add may hold
+// 2^30 granules (4 TiB) on a 256-CU chip: more than its memory.
+constexpr uint64_t kHistMaxGranules = 1ull << 19;
+uint32_t hist_grid_max(int cus) { return (uint32_t)(cus > 0 ? cus : 256) * 8; }
+
+uint32_t grid_for(uint64_t n) {   // grid-stride kernels: up to 2048 workgroups of 256
+    const uint64_t g = (n + 255) / 256;
+    return (uint32_t)(g < 2048 ? (g ? g : 1) : 2048);
+}
+
+}  // namespace
+
+hipError_t launch_measure_granules(const MeasurePlan &P, const uint8_t *src, uint64_t stride, int waves, void *rec,
+                                   hipStream_t s) {
+    (void)hipGetLastError();
+    MeasureFp *rfp = reinterpret_cast<MeasureFp *>(rec);
+    uint32_t *rz = reinterpret_cast<uint32_t *>((uint8_t *)rec + measure_record_zero_offset(P.records));
+    for (uint64_t iy = 0; iy < P.ny; ++iy) {
+        for (uint64_t ix = 0; ix < P.nx; ++ix) {
+            uint64_t x0, y0;
+            uint32_t gx, gy;
+            measure_sub_launch(P, ix, iy, &x0, &gx, &y0, &gy);
+            const dim3 g(gx, gy);
+            const uint8_t *p = src + y0 * stride;
+            const uint64_t rb = y0 * P.gpo;
+            if (waves == 1)
+                hipLaunchKernelGGL((k_measure<1>), g, dim3(64), 0, s, p, stride, P.len, (uint32_t)x0, P.gpb, P.gpo, rb,
+                                   rfp, rz);
+            else if (waves == 4)
+                hipLaunchKernelGGL((k_measure<4>), g, dim3(256), 0, s, p, stride, P.len, (uint32_t)x0, P.gpb, P.gpo,
+                                   rb, rfp, rz);
+            else
+                hipLaunchKernelGGL((k_measure<2>), g, dim3(128), 0, s, p, stride, P.len, (uint32_t)x0, P.gpb, P.gpo,
+                                   rb, rfp, rz);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_measure_blocks(const MeasurePlan &P, uint64_t block_bytes, const void *rec, MeasureFp *fp,
+                                 uint64_t *zero_total, hipStream_t s) {
+    (void)hipGetLastError();
+    const MeasureFp *rfp = reinterpret_cast<const MeasureFp *>(rec);
+    const uint32_t *rz = reinterpret_cast<const uint32_t *>((const uint8_t *)rec + measure_record_zero_offset(P.records));
+    const uint64_t per = P.gpb < 16 ? 256 : 4;   // blocks per workgroup
+    const uint64_t grid = (P.slots + per - 1) / per;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (P.gpb < 16)
+        hipLaunchKernelGGL(k_measure_blocks, dim3((uint32_t)grid), dim3(256), 0, s, rfp, rz, P.slots, P.bpo, P.gpo,
+                           P.gpb, block_bytes, P.last_block, fp, zero_total);
+    else
+        hipLaunchKernelGGL(k_measure_blocks_wave, dim3((uint32_t)grid), dim3(256), 0, s, rfp, rz, P.slots, P.bpo,
+                           P.gpo, P.gpb, block_bytes, P.last_block, fp, zero_total);
+    return hipGetLastError();
+}
+
+uint64_t measure_hist_part_bytes(int cus) { return (uint64_t)hist_grid_max(cus) * 256 * sizeof(uint32_t); }
+
+hipError_t launch_byte_hist(const MeasurePlan &P, const uint8_t *src, uint64_t stride, int cus, void *part,
+                            uint64_t *hist, hipStream_t s) {
+    (void)hipGetLastError();
+    const uint64_t gmax = hist_grid_max(cus);
+    const uint32_t grid = (uint32_t)(P.records < gmax ? P.records : gmax);
+    if (P.records > (uint64_t)grid * kHistMaxGranules) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_byte_hist, dim3(grid), dim3(256), 0, s, src, stride, P.len, P.gpo, P.records,
+                       reinterpret_cast<uint32_t *>(part));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_hist_reduce, dim3(1), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(part), grid, hist);
+    return hipGetLastError();
+}
+
+hipError_t launch_measure_distinct(const MeasureFp *fp, uint64_t n, void *work, size_t *tmp_bytes,
+                                   uint64_t *distinct, hipStream_t s) {
+    if (n > 0x7FFFFFFFull) return hipErrorInvalidValue;   // hipCUB counts items in an int
+    const uint64_t ab = measure_sort_array_bytes(n);
+    uint64_t *lo_a = reinterpret_cast<uint64_t *>(work), *hi_a = nullptr, *lo_b = nullptr, *hi_b = nullptr;
+    void *tmp = nullptr;
+    if (work) {
+        hi_a = reinterpret_cast<uint64_t *>((uint8_t *)work + ab);
+        lo_b = reinterpret_cast<uint64_t *>((uint8_t *)work + 2 * ab);
+        hi_b = reinterpret_cast<uint64_t *>((uint8_t *)work + 3 * ab);
+        tmp = (uint8_t *)work + 4 * ab;
+    }
+    if (!work) {
+        *tmp_bytes = 0;
+        return hipcub::DeviceRadixSort::SortPairs(nullptr, *tmp_bytes, lo_a, lo_b, hi_a, hi_b, (int)n, 0, 64, s);
+    }
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_fp_split, dim3(grid_for(n)), dim3(256), 0, s, fp, n, lo_a, hi_a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    // stable LSD passes: by the low half, then by the high half
+    e = hipcub::DeviceRadixSort::SortPairs(tmp, *tmp_bytes, lo_a, lo_b, hi_a, hi_b, (int)n, 0, 64, s);
+    if (e != hipSuccess) return e;
+    e = hipcub::DeviceRadixSort::SortPairs(tmp, *tmp_bytes, hi_b, hi_a, lo_b, lo_a, (int)n, 0, 64, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_count_distinct, dim3(grid_for(n)), dim3(256), 0, s, lo_a, hi_a, n, distinct);
+    return hipGetLastError();
+}
+
+}  // namespace s3dg

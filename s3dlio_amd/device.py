@@ -72,6 +72,47 @@ class VerifyResult:
         return cls(int(r.mismatched_bytes), int(r.mismatched_blocks), None if first == 2**64 - 1 else first)
 
 
+@dataclass(frozen=True)
+class MeasureResult:
+    """s3dg_measure_result: what a payload looks like to a store that
+    deduplicates and compresses at the measured block size."""
+    bytes: int = 0            # payload bytes measured (stride gaps excluded)
+    zero_bytes: int = 0
+    blocks: int = 0           # blocks measured, ragged last blocks included
+    unique_blocks: int = 0    # distinct among them (bytes and length)
+    hist: tuple | None = None   # 256 byte counts, or None when not asked for
+
+    @property
+    def zero_fraction(self) -> float:
+        return self.zero_bytes / self.bytes if self.bytes else 0.0
+
+    @property
+    def unique_fraction(self) -> float:
+        """unique / blocks: the reference tests' "dedup ratio" (1/dedup expected)."""
+        return self.unique_blocks / self.blocks if self.blocks else 0.0
+
+    @property
+    def dedup_ratio(self) -> float:
+        """blocks / unique: what a dedup engine at this block size saves (n : 1)."""
+        return self.blocks / self.unique_blocks if self.unique_blocks else 0.0
+
+    @property
+    def entropy_bits(self) -> float | None:
+        """Shannon entropy in bits per byte from the histogram; None without one."""
+        if self.hist is None:
+            return None
+        n = sum(self.hist)
+        if n == 0:
+            return 0.0
+        p = np.array([c for c in self.hist if c], dtype=np.float64) / n
+        return float(-(p * np.log2(p)).sum())
+
+    @classmethod
+    def _of(cls, r, hist: bool) -> "MeasureResult":
+        return cls(int(r.bytes), int(r.zero_bytes), int(r.blocks), int(r.unique_blocks),
+                   tuple(int(v) for v in r.hist) if hist else None)
+
+
 def _ptr(x) -> int:
     """Device pointer of a torch CUDA tensor (contiguous) or a raw int."""
     if isinstance(x, int):
@@ -447,6 +488,30 @@ class Context:
              int(dedup), fn, fd, int(seed_base) & (2**64 - 1), int(first_obj), self._s(stream), ctypes.byref(r))
         return VerifyResult._of(r)
 
+    # -- measurement (read-only) ---------------------------------------------------
+    # How many blocks of `block_bytes` are distinct and how many bytes are zero
+    # (hist=True: the byte histogram too), whatever wrote the bytes: no seed is
+    # needed.  Blocks are cut from each object's start; a ragged last block is a
+    # block of its own.
+    def measurer(self, block_bytes: int = 4096, hist: bool = False) -> "Measure":
+        """An accumulating handle: add / add_stream / add_range on any stream,
+        then result()."""
+        return Measure(self, block_bytes, hist)
+
+    def measure(self, src, nbytes: int | None = None, block_bytes: int = 4096, hist: bool = False,
+                stream=None) -> MeasureResult:
+        """One object of `nbytes` at src."""
+        with self.measurer(block_bytes, hist) as m:
+            m.add(src, nbytes, stream=stream)
+            return m.result()
+
+    def measure_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None,
+                       block_bytes: int = 4096, hist: bool = False, stream=None) -> MeasureResult:
+        """n_objs equal objects as fill_stream lays them out; stride gaps are never read."""
+        with self.measurer(block_bytes, hist) as m:
+            m.add_stream(src, obj_size, n_objs, stride, stream=stream)
+            return m.result()
+
     def write_ceiling(self, dst, nbytes: int | None = None, pattern: int = 0xA5A5A5A5,
                       stream=None) -> None:
         n = _nbytes(dst) if nbytes is None else int(nbytes)
@@ -478,6 +543,66 @@ class Context:
         n = ctypes.c_uint64()
         call("s3dg_stream_state_count", self._h, ctypes.byref(n))
         return n.value
+
+
+class Measure:
+    """s3dg_measure: a measurement that accumulates over calls and streams
+    (Context.measurer).  The adds are asynchronous on their stream and ordered
+    like a fill, so a following launch on the same stream may overwrite the
+    buffer; result() waits for them and leaves the handle unchanged."""
+
+    def __init__(self, ctx: Context, block_bytes: int = 4096, hist: bool = False):
+        self._ctx = ctx
+        self.block_bytes = int(block_bytes)
+        self.hist = bool(hist)
+        h = c_vp()
+        call("s3dg_measure_create", ctx._h, self.block_bytes, 1 if hist else 0, ctypes.byref(h))
+        self._h = h
+
+    def add(self, src, nbytes: int | None = None, stream=None) -> None:
+        """One object of `nbytes` at src."""
+        n = _nbytes(src) if nbytes is None else int(nbytes)
+        self.add_stream(src, n, 1, stride=0, stream=stream)   # one object: no stride to align
+
+    def add_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None, stream=None) -> None:
+        """n_objs objects of obj_size bytes, object j at src + j*stride."""
+        stride = obj_size if stride is None else stride
+        need = (int(n_objs) - 1) * int(stride) + int(obj_size) if n_objs > 0 and obj_size > 0 else 0
+        call("s3dg_measure_add_stream", self._h, self._ctx._src(src, need), int(obj_size), int(stride),
+             int(n_objs), self._ctx._s(stream))
+
+    def add_range(self, src, obj_size: int, blk_lo: int, blk_hi: int, stream=None) -> None:
+        """Blocks [blk_lo, blk_hi) (units of block_bytes) of one obj_size-byte
+        object, block blk_lo at src."""
+        hi = min(int(blk_hi) * self.block_bytes, int(obj_size))
+        need = max(0, hi - int(blk_lo) * self.block_bytes)
+        call("s3dg_measure_add_range", self._h, self._ctx._src(src, need), int(obj_size), int(blk_lo),
+             int(blk_hi), self._ctx._s(stream))
+
+    def result(self) -> MeasureResult:
+        r = _lib.MeasureRec()
+        call("s3dg_measure_get", self._h, ctypes.byref(r))
+        return MeasureResult._of(r, self.hist)
+
+    def reset(self) -> None:
+        call("s3dg_measure_reset", self._h)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            call("s3dg_measure_destroy", self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def xoshiro_jump(state, n: int) -> list[int]:

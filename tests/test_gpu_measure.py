@@ -1,0 +1,510 @@
+"""GPU: payload measurement (k_measure, k_measure_blocks, the distinct count,
+k_byte_hist and the surfaces over them).
+
+Every expected number comes from numpy on host bytes, never from a restatement
+of the fingerprint: distinct blocks are `len({bytes(b) for b in blocks})` with
+the blocks cut per object (a ragged last block is a block of its own), zeros
+are `np.count_nonzero(a == 0)`, the histogram is `np.bincount`.  Generated
+payloads come from the C oracle (oracle/oracle_c.py).  Every assertion is exact.
+"""
+import functools
+import threading
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+BLK = 4096
+MiB = 1 << 20
+SIZES = [1, 15, 16, 17, 4095, 4096, 4097, 8292, 3 * 4096 + 2080, 64 * 4096, 64 * 4096 + 100, 3 * MiB + 4097]
+DEDUPS = [0, 1, 2, 3, 7]
+COMPRESS = [1, 2, 3, (3, 2), 128]
+HOST_CHUNK = 64 << 20          # the host path's staging chunk
+
+
+@pytest.fixture(scope="module")
+def S():
+    import s3dlio_amd
+    return s3dlio_amd
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch
+    return torch
+
+
+@pytest.fixture(scope="module")
+def base(golden_base):
+    return np.frombuffer(golden_base, np.uint8)
+
+
+@pytest.fixture(scope="module")
+def wave_ctx(S, gpu_ctx):
+    ctxs = {w: S.Context(0, base_seed=S.DEFAULT_BASE_SEED, waves_per_block=w) for w in (1, 2, 4)}
+    yield ctxs
+    for c in ctxs.values():
+        c.close()
+
+
+def expect(S, objs, block_bytes, hist=False):
+    """The result of measuring the objects (host arrays), from numpy."""
+    seen, blocks, nbytes, zeros = set(), 0, 0, 0
+    h = np.zeros(256, np.int64)
+    for a in objs:
+        a = np.ascontiguousarray(a, np.uint8)
+        mv = memoryview(a)
+        for o in range(0, a.size, block_bytes):
+            seen.add(bytes(mv[o:o + block_bytes]))
+            blocks += 1
+        nbytes += a.size
+        zeros += int(np.count_nonzero(a == 0))
+        if hist:
+            h += np.bincount(a, minlength=256)
+    return S.MeasureResult(nbytes, zeros, blocks, len(seen), tuple(int(v) for v in h) if hist else None)
+
+
+def np_entropy(h):
+    h = np.asarray(h, np.float64)
+    p = h[h > 0] / h.sum()
+    return float(-(p * np.log2(p)).sum())
+
+
+def dev(torch, a):
+    return torch.from_numpy(np.array(a, dtype=np.uint8, copy=True)).to("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def exp(S, oracle, base):
+    """Oracle bytes and their expected results, computed once per argument set."""
+    class E:
+        @staticmethod
+        @functools.lru_cache(maxsize=None)
+        def controlled(size, dedup, compress, entropy=42):
+            fn, fd = S.compress_ratio(compress)
+            a = oracle.fill_controlled(size, dedup, fn, fd, entropy, base)
+            a.setflags(write=False)
+            return a
+
+        @staticmethod
+        @functools.lru_cache(maxsize=None)
+        def dgen(size, dedup, compress, seed=7):
+            fn, fd = S.compress_ratio(compress)
+            a = oracle.dgen_fill(size, dedup, fn, fd, seed)
+            a.setflags(write=False)
+            return a
+
+        @staticmethod
+        @functools.lru_cache(maxsize=None)
+        def controlled_result(size, dedup, compress, block_bytes):
+            return expect(S, [E.controlled(size, dedup, compress)], block_bytes)
+
+        @staticmethod
+        @functools.lru_cache(maxsize=None)
+        def dgen_result(size, dedup, compress, block_bytes):
+            return expect(S, [E.dgen(size, dedup, compress)], block_bytes)
+    return E
+
+
+@pytest.fixture(scope="module")
+def dgen_dev(torch, exp):
+    """The DG1 payloads of section 2 on the device, uploaded once."""
+    @functools.lru_cache(maxsize=None)
+    def get(size, dedup, compress):
+        return dev(torch, exp.dgen(size, dedup, compress))
+    return get
+
+
+# ---- 1. generated payloads at 4 KiB blocks ----------------------------------------
+
+@pytest.mark.parametrize("waves", [1, 2, 4])
+@pytest.mark.parametrize("compress", COMPRESS, ids=str)
+def test_controlled_4k(S, torch, wave_ctx, exp, waves, compress):
+    ctx = wave_ctx[waves]
+    for size in SIZES:
+        for dedup in DEDUPS:
+            t = dev(torch, exp.controlled(size, dedup, compress))
+            got = ctx.measure(t, block_bytes=BLK)
+            assert got == exp.controlled_result(size, dedup, compress, BLK), (size, dedup)
+            if size % BLK == 0:   # the generator's closed form; a ragged tail is one block more
+                assert got.unique_blocks == S.unique_blocks(size // BLK, dedup), (size, dedup)
+
+
+# ---- 2. DG1 -------------------------------------------------------------------------
+
+@pytest.mark.parametrize("size,dedup,compress,block_bytes,unique,blocks", [
+    (8 * MiB, 2, 1, MiB, 4, 8),
+    (8 * MiB, 3, 2, MiB, 3, 8),
+    (8 * MiB, 3, 2, BLK, 385, 2048),
+    (8 * MiB + 5, 2, 2, MiB, 6, 9),      # the closed form gives 5; the 5-byte tail is the sixth
+    (64 * MiB, 2, 1, MiB, 32, 64),       # the reference's test_data_dedup_compress1
+    (64 * MiB, 2, 1, BLK, 8192, 16384),
+    (8 * MiB, 3, 2, 8192, None, 1024),
+    (8 * MiB, 3, 2, 65536, None, 128),
+    (8 * MiB + 5, 2, 2, 8192, None, 1025),
+    (8 * MiB + 5, 2, 2, 65536, None, 129),
+    (64 * MiB, 2, 1, 65536, None, 1024),
+])
+def test_dgen(S, gpu_ctx, exp, dgen_dev, size, dedup, compress, block_bytes, unique, blocks):
+    got = gpu_ctx.measure(dgen_dev(size, dedup, compress), block_bytes=block_bytes)
+    assert got == exp.dgen_result(size, dedup, compress, block_bytes)
+    assert got.blocks == blocks
+    if unique is not None:
+        assert got.unique_blocks == unique
+
+
+def test_dgen_zero_fraction(S, torch, gpu_ctx, exp, dgen_dev):
+    """The reference tests' own tolerance: |z - (c-1)/c| < 0.05."""
+    r1 = gpu_ctx.measure(dgen_dev(64 * MiB, 2, 1), block_bytes=MiB)
+    assert r1.zero_bytes == exp.dgen_result(64 * MiB, 2, 1, MiB).zero_bytes
+    assert abs(r1.zero_fraction - 0.0) < 0.05
+    r2 = gpu_ctx.measure(dev(torch, exp.dgen(16 * MiB, 1, 2)), block_bytes=MiB)
+    assert r2 == exp.dgen_result(16 * MiB, 1, 2, MiB)
+    assert abs(r2.zero_fraction - 0.5) < 0.05
+
+
+# ---- 3. crafted blocks ---------------------------------------------------------------
+
+def variants(a):
+    """(name, block) pairs: copies of block `a` changed in one small way inside its first 4 KiB."""
+    out = []
+
+    def var(name, f):
+        b = a.copy()
+        f(b)
+        assert not np.array_equal(a, b), name
+        out.append((name, b))
+
+    for off in (0, 15, 16, 2047, 2048, 4095):
+        for bit in range(8):
+            def flip(b, off=off, bit=bit):
+                b[off] ^= 1 << bit
+            var(f"bit{bit}@{off}", flip)
+
+    def swap(b, i, j, w):
+        x = b[i:i + w].copy()
+        b[i:i + w] = b[j:j + w]
+        b[j:j + w] = x
+    for p, q in ((0, 1), (0, 64), (3, 255)):
+        var(f"pieces{p},{q}", lambda b, p=p, q=q: swap(b, 16 * p, 16 * q, 16))
+
+    def rotate(b):
+        b[:4096] = np.roll(b[:4096], 16)
+    var("rotate", rotate)
+    var("dwords", lambda b: swap(b, 16 * 5 + 0, 16 * 5 + 8, 4))
+    var("adjacent dwords", lambda b: swap(b, 16 * 9 + 4, 16 * 9 + 8, 4))
+    var("halves", lambda b: swap(b, 16 * 7, 16 * 7 + 8, 8))
+    var("bytes", lambda b: swap(b, 16 * 11 + 4, 16 * 11 + 6, 1))
+
+    def move(b, p, q, k):
+        b[16 * p + k] += 1
+        b[16 * q + k] -= 1
+    for p, q, k in ((2, 3, 0), (2, 66, 5), (10, 200, 15)):
+        var(f"move{p},{q},{k}", lambda b, p=p, q=q, k=k: move(b, p, q, k))
+    return out
+
+
+@pytest.mark.parametrize("block_bytes", [4096, 8192])
+def test_crafted_pairs(S, torch, gpu_ctx, block_bytes):
+    rng = np.random.default_rng(1234 + block_bytes)
+    a = rng.integers(0, 256, block_bytes, dtype=np.uint8)
+    for p, q, k in ((2, 3, 0), (2, 66, 5), (10, 200, 15)):   # room for the +1 / -1 of "move"
+        a[16 * p + k] = 100
+        a[16 * q + k] = 100
+    r = gpu_ctx.measure(dev(torch, np.concatenate([a, a])), block_bytes=block_bytes)
+    assert (r.blocks, r.unique_blocks) == (2, 1)
+    for name, b in variants(a):
+        both = np.concatenate([a, b])
+        r = gpu_ctx.measure(dev(torch, both), block_bytes=block_bytes)
+        assert r == expect(S, [both], block_bytes), name
+        assert (r.blocks, r.unique_blocks) == (2, 2), name
+    # all variants and the original at once
+    alls = np.concatenate([a] + [b for _, b in variants(a)] + [a])
+    r = gpu_ctx.measure(dev(torch, alls), block_bytes=block_bytes)
+    assert r == expect(S, [alls], block_bytes)
+    assert r.unique_blocks == r.blocks - 1
+
+
+@pytest.mark.parametrize("block_bytes", [8192, MiB])
+def test_granule_order(S, torch, gpu_ctx, block_bytes):
+    rng = np.random.default_rng(99)
+    a = rng.integers(0, 256, block_bytes, dtype=np.uint8)
+    g = a.reshape(-1, BLK)
+    swapped = g.copy()
+    swapped[[0, 1]] = swapped[[1, 0]]
+    rolled = np.roll(g, 1, axis=0)
+    for name, b in (("swapped", swapped.reshape(-1)), ("rolled", rolled.reshape(-1))):
+        both = np.concatenate([a, b])
+        r = gpu_ctx.measure(dev(torch, both), block_bytes=block_bytes)
+        assert r == expect(S, [both], block_bytes), name
+        assert (r.blocks, r.unique_blocks) == (2, 2), name
+    same = np.concatenate([a, a, a])
+    r = gpu_ctx.measure(dev(torch, same), block_bytes=block_bytes)
+    assert (r.blocks, r.unique_blocks) == (3, 1)
+
+
+@pytest.mark.parametrize("block_bytes", [4096, 8192, 65536])
+def test_constant_blocks(S, torch, gpu_ctx, block_bytes):
+    n = 64 * 1024
+    z, f = np.zeros(n, np.uint8), np.full(n, 0xFF, np.uint8)
+    r = gpu_ctx.measure(dev(torch, z), block_bytes=block_bytes)
+    assert r == expect(S, [z], block_bytes) and r.unique_blocks == 1 and r.zero_bytes == n
+    r = gpu_ctx.measure(dev(torch, f), block_bytes=block_bytes)
+    assert r == expect(S, [f], block_bytes) and r.unique_blocks == 1 and r.zero_bytes == 0
+    zf = np.concatenate([z, f])
+    r = gpu_ctx.measure(dev(torch, zf), block_bytes=block_bytes)
+    assert r == expect(S, [zf], block_bytes) and r.unique_blocks == 2 and r.zero_bytes == n
+
+
+# ---- 4. ragged tails and streams ---------------------------------------------------------
+
+def strided(objs, stride, poison):
+    """The objects at a stride, every gap (the one after the last object too) filled with poison."""
+    buf = np.empty(stride * len(objs), np.uint8)
+    for j, a in enumerate(objs):
+        buf[j * stride:j * stride + a.size] = a
+        buf[j * stride + a.size:(j + 1) * stride] = (poison + 37 * j) & 0xFF
+    return buf
+
+
+@pytest.mark.parametrize("waves", [1, 2, 4])
+@pytest.mark.parametrize("block_bytes", [4096, 8192])
+def test_ragged_stream_ignores_gaps(S, torch, wave_ctx, block_bytes, waves):
+    ctx = wave_ctx[waves]
+    rng = np.random.default_rng(5)
+    size, stride = 12288 + 100, 12288 + 100 + 4096 + 12   # a 16-byte aligned stride with a > 4 KiB gap
+    objs = [rng.integers(0, 256, size, dtype=np.uint8) for _ in range(5)]
+    objs[3][:8192] = objs[1][:8192]      # shared blocks between objects
+    objs[4][-100:] = objs[0][-100:]      # at 4096: a shared 100-byte tail
+    want = expect(S, objs, block_bytes)
+    got = [ctx.measure_stream(dev(torch, strided(objs, stride, p)), size, 5, stride, block_bytes=block_bytes)
+           for p in (0x00, 0xA5)]
+    assert got[0] == want and got[1] == want
+    assert want.bytes == 5 * size
+
+
+def test_tails(S, torch, gpu_ctx):
+    rng = np.random.default_rng(6)
+    tail = rng.integers(0, 256, 100, dtype=np.uint8)
+    objs = [np.concatenate([rng.integers(0, 256, BLK, dtype=np.uint8), tail]) for _ in range(4)]
+    stride = BLK + 112
+    r = gpu_ctx.measure_stream(dev(torch, strided(objs, stride, 0x11)), BLK + 100, 4, stride)
+    assert r == expect(S, objs, BLK) and (r.blocks, r.unique_blocks) == (8, 5)   # identical tails count once
+    a = rng.integers(0, 256, BLK, dtype=np.uint8)
+    one = np.concatenate([a, a[:100]])     # a tail equal to the start of a full block is still its own block
+    r = gpu_ctx.measure(dev(torch, one))
+    assert r == expect(S, [one], BLK) and (r.blocks, r.unique_blocks) == (2, 2)
+    z = np.zeros(BLK + 100, np.uint8)      # the same with zeros: padding must not make them equal
+    r = gpu_ctx.measure(dev(torch, z))
+    assert r == expect(S, [z], BLK) and (r.blocks, r.unique_blocks) == (2, 2)
+    for v in (0, 7):
+        b = np.full(1, v, np.uint8)
+        r = gpu_ctx.measure(dev(torch, np.concatenate([b, np.full(15, 0xEE, np.uint8)])), nbytes=1)
+        assert r == expect(S, [b], BLK) and (r.bytes, r.blocks, r.unique_blocks, r.zero_bytes) == (1, 1, 1, int(v == 0))
+
+
+def test_stream_across_object_split(S, torch, gpu_ctx):
+    """More than 65 535 objects: the launch is split along the objects."""
+    n = 65535 + 3
+    rng = np.random.default_rng(8)
+    table = rng.integers(0, 256, (1000, BLK), dtype=np.uint8)
+    table[17, :2048] = 0
+    idx = np.arange(n) % 1000
+    idx[-3:] = (998, 1, 998)
+    buf = table[idx].reshape(-1)
+    r = gpu_ctx.measure_stream(dev(torch, buf), BLK, n)
+    assert r == expect(S, list(buf.reshape(n, BLK)), BLK)
+    assert (r.blocks, r.unique_blocks) == (n, 1000)
+
+
+def test_object_across_granule_split(S, torch, gpu_ctx):
+    """One object of more than 2^22 granules (16 GiB): the launch is split along the granules.
+    A zeroed device buffer with three marker bytes; the expected numbers follow from where they
+    are (no host copy of 16 GiB): 1 MiB blocks 5 and 16384 carry the same byte at the same
+    offset, so they are one block, and block 16384 starts the second sub-launch."""
+    n = (16384 + 1) * MiB + 100
+    t = torch.zeros(n + 12, dtype=torch.uint8, device="cuda:0")
+    for pos in (5 * MiB + 100, 16384 * MiB + 100, 100 * MiB + 3 * BLK + 100):
+        t[pos] = 7
+    r = gpu_ctx.measure(t, nbytes=n, block_bytes=MiB, hist=True)
+    hist = [0] * 256
+    hist[0], hist[7] = n - 3, 3
+    assert r == S.MeasureResult(n, n - 3, 16386, 4, tuple(hist))   # zeros, two marker blocks, the 100-byte tail
+    r = gpu_ctx.measure(t, nbytes=n, block_bytes=BLK)
+    assert (r.bytes, r.zero_bytes, r.blocks, r.unique_blocks) == (n, n - 3, 16385 * 256 + 1, 3)
+    del t
+    torch.cuda.empty_cache()
+
+
+# ---- 5. accumulation ------------------------------------------------------------------------
+
+def test_adds_reuse_one_buffer(S, torch, gpu_ctx, oracle, base):
+    """Three adds over one device buffer that fills on the same stream overwrite, no sync between."""
+    size, n, stride = 8292, 4, 8304
+    fn, fd = S.compress_ratio(2)
+    seeds = (1000, 2000, 3000)
+    host = [oracle.fill_stream(size, n, 2, fn, fd, sb, 0, base, stride=stride) for sb in seeds]
+    objs = [h[j * stride:j * stride + size] for h in host for j in range(n)]
+    t = torch.zeros(stride * n, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    st = torch.cuda.Stream()
+    with gpu_ctx.measurer(BLK) as m:
+        for sb in seeds:
+            gpu_ctx.fill_stream(t, size, n, stride, dedup=2, compress=2, seed_base=sb, stream=st)
+            m.add_stream(t, size, n, stride, stream=st)
+        r = m.result()
+        assert r == expect(S, objs, BLK)
+        # the same seeds again: twice the blocks, nothing new
+        for sb in seeds:
+            gpu_ctx.fill_stream(t, size, n, stride, dedup=2, compress=2, seed_base=sb, stream=st)
+            m.add_stream(t, size, n, stride, stream=st)
+        r2 = m.result()
+        assert (r2.blocks, r2.bytes, r2.zero_bytes) == (2 * r.blocks, 2 * r.bytes, 2 * r.zero_bytes)
+        assert r2.unique_blocks == r.unique_blocks
+    one = gpu_ctx.measure_stream(dev(torch, np.concatenate([strided([o], stride, 0) for o in objs])), size, 3 * n,
+                                 stride)
+    assert one == r
+    st.synchronize()
+
+
+@pytest.mark.parametrize("block_bytes", [4096, 65536])
+def test_ranges_equal_the_whole(S, torch, gpu_ctx, exp, block_bytes):
+    size = 3 * MiB + 4097
+    a = exp.controlled(size, 3, 2)
+    t = dev(torch, a)
+    nb = -(-size // block_bytes)
+    cuts = [0, nb // 7, nb // 7 + 1, nb // 2, nb + 5]
+    with gpu_ctx.measurer(block_bytes) as m:
+        for lo, hi in zip(cuts, cuts[1:]):
+            m.add_range(t[lo * block_bytes:], size, lo, hi)
+        m.add_range(t, size, 3, 3)             # empty ranges add nothing
+        m.add_range(t, size, nb, nb + 1)
+        r = m.result()
+    assert r == expect(S, [a], block_bytes) == gpu_ctx.measure(t, block_bytes=block_bytes)
+
+
+def test_two_streams_two_threads(S, torch, gpu_ctx, exp):
+    parts = [exp.controlled(64 * 4096 + 100, 2, 2), exp.controlled(3 * MiB + 4097, 3, 1)]
+    ts = [dev(torch, p) for p in parts]
+    torch.cuda.synchronize()               # the uploads ran on the default stream
+    errs = []
+    with gpu_ctx.measurer(BLK) as m:
+        def work(k):
+            try:
+                st = torch.cuda.Stream()
+                for _ in range(4):
+                    m.add(ts[k], stream=st)
+            except Exception as e:   # pragma: no cover
+                errs.append(e)
+        th = [threading.Thread(target=work, args=(k,)) for k in range(2)]
+        for x in th:
+            x.start()
+        for x in th:
+            x.join()
+        assert not errs
+        r = m.result()
+    want = expect(S, parts, BLK)
+    assert (r.bytes, r.zero_bytes, r.blocks) == (4 * want.bytes, 4 * want.zero_bytes, 4 * want.blocks)
+    assert r.unique_blocks == want.unique_blocks
+
+
+def test_result_is_not_destructive(S, torch, gpu_ctx, exp):
+    a, b = exp.controlled(64 * 4096, 2, 2), exp.controlled(8292, 1, 1)
+    with gpu_ctx.measurer(BLK, hist=True) as m:
+        assert m.result() == S.MeasureResult(hist=(0,) * 256)
+        m.add(dev(torch, a))
+        r1 = m.result()
+        assert r1 == m.result() == expect(S, [a], BLK, hist=True)
+        m.add(dev(torch, b))
+        assert m.result() == expect(S, [a, b], BLK, hist=True)
+        m.reset()
+        assert m.result() == S.MeasureResult(hist=(0,) * 256)
+        m.add(dev(torch, b))
+        assert m.result() == expect(S, [b], BLK, hist=True)
+    with gpu_ctx.measurer(BLK) as m:
+        m.add_stream(0, 0, 5)                  # zero-length adds launch nothing, whatever the pointer
+        m.add_stream(0, 4096, 0)
+        assert m.result() == S.MeasureResult()
+
+
+def test_array_growth(S, torch, gpu_ctx, oracle, base):
+    """65 536 fingerprints added in uneven pieces: the array doubles several times."""
+    size = 256 * MiB
+    a = oracle.fill_stream(size, 1, 4, 0, 1, 77, 0, base, threads=8)
+    t = dev(torch, a)
+    nb = size // BLK
+    cuts = [0, 1, 1000, 5000, 5001, 30000, nb]
+    with gpu_ctx.measurer(BLK) as m:
+        for lo, hi in zip(cuts, cuts[1:]):
+            m.add_range(t[lo * BLK:], size, lo, hi)
+        r = m.result()
+    assert r == expect(S, [a], BLK)
+    assert (r.blocks, r.unique_blocks) == (nb, S.unique_blocks(nb, 4))
+
+
+# ---- 6. histogram ----------------------------------------------------------------------------
+
+def test_histogram(S, torch, gpu_ctx, exp):
+    rng = np.random.default_rng(3)
+    cases = [exp.controlled(64 * 4096 + 100, 1, 1), exp.controlled(64 * 4096 + 100, 2, 3), exp.dgen(8 * MiB, 2, 1),
+             np.zeros(65536, np.uint8), np.full(65536, 0xFF, np.uint8), np.full(1, 9, np.uint8),
+             np.zeros(1, np.uint8), rng.integers(0, 4, 100001, dtype=np.uint8)]
+    for a in cases:
+        pad = np.concatenate([a, np.full(-a.size % 16, 0xEE, np.uint8)])
+        r = gpu_ctx.measure(dev(torch, pad), nbytes=a.size, hist=True)
+        assert r == expect(S, [a], BLK, hist=True), a.size
+        assert r.hist == tuple(int(v) for v in np.bincount(a, minlength=256))
+        assert abs(r.entropy_bits - np_entropy(r.hist)) <= 1e-12
+        plain = gpu_ctx.measure(dev(torch, pad), nbytes=a.size)
+        assert plain.hist is None and plain.entropy_bits is None and plain.zero_bytes == r.zero_bytes
+
+
+def test_histogram_ragged_stream(S, torch, gpu_ctx):
+    rng = np.random.default_rng(4)
+    size, stride = 12288 + 100, 12288 + 100 + 4096 + 12
+    objs = [rng.integers(0, 7, size, dtype=np.uint8) for _ in range(5)]
+    want = expect(S, objs, BLK, hist=True)
+    for p in (0x00, 0x03):
+        assert gpu_ctx.measure_stream(dev(torch, strided(objs, stride, p)), size, 5, stride, hist=True) == want
+
+
+# ---- 7. host buffers ---------------------------------------------------------------------------
+
+def test_measure_data_buffers(S, exp):
+    a = exp.controlled(64 * 4096 + 100, 2, 2)
+    want = expect(S, [a], BLK, hist=True)
+    assert S.measure_data(bytearray(a.tobytes()), hist=True) == want
+    assert S.measure_data(a.tobytes(), hist=True) == want                  # read-only bytes
+    shifted = np.empty(a.size + 1, np.uint8)
+    shifted[1:] = a
+    assert S.measure_data(shifted[1:], hist=True) == want                  # a view at offset 1
+    assert S.measure_data(a) == expect(S, [a], BLK)
+    assert S.measure_data(b"") == S.MeasureResult()
+
+
+@pytest.mark.parametrize("block_bytes", [4096, MiB])
+def test_measure_data_across_the_chunk_edge(S, exp, block_bytes):
+    a = exp.dgen(HOST_CHUNK + 4097, 2, 2)
+    assert S.measure_data(a, block_bytes=block_bytes) == expect(S, [a], block_bytes)
+
+
+# ---- 8. refusals on the device ---------------------------------------------------------------------
+
+def test_refusals(S, torch, gpu_ctx):
+    t = torch.zeros(3 * 8192, dtype=torch.uint8, device="cuda:0")
+    with gpu_ctx.measurer(BLK) as m:
+        with pytest.raises(ValueError, match="16-byte aligned"):
+            m.add_stream(t[8:], 4096, 2, 4096)
+        with pytest.raises(ValueError, match="16-byte aligned"):
+            m.add_stream(t, 4096, 2, 4104)
+        with pytest.raises(ValueError, match="overlap"):
+            m.add_stream(t, 8192, 2, 4096)
+        with pytest.raises(ValueError, match="16-byte aligned"):
+            m.add_range(t[4:], 8192, 0, 1)
+        with pytest.raises(ValueError, match="holds"):
+            m.add_stream(t, 8192, 4)
+        assert m.result() == S.MeasureResult()
+    for bb in (0, 4095, 6000, 2**31):
+        with pytest.raises(ValueError, match="block_bytes"):
+            gpu_ctx.measurer(bb)
