@@ -508,3 +508,277 @@ def test_refusals(S, torch, gpu_ctx):
     for bb in (0, 4095, 6000, 2**31):
         with pytest.raises(ValueError, match="block_bytes"):
             gpu_ctx.measurer(bb)
+
+
+# ---- 9. block sizes that are no power of two -----------------------------------------------------
+# gpb = 3, 5, 15 (the last one-thread-per-block size), 17 (the first odd one-wave-per-block size)
+# and 65 (that kernel's second lap).
+
+ODD_BB = [12288, 20480, 61440, 69632, 266240]
+TABLE_SEQ = [0, 1, 2, 1, 0, 3, 3, 4, 5, 6, 2]
+TABLE_K = 7
+TABLE_TAIL = 4096 + 100
+
+
+@functools.lru_cache(maxsize=None)
+def table_objects(block_bytes):
+    """Five objects over one table of K random blocks (the first half of block 3 zeroed, block 6
+    equal to block 5 up to its last byte): object j is the blocks TABLE_SEQ rotated by j, then a
+    ragged tail equal to the start of block 1."""
+    rng = np.random.default_rng(4000 + block_bytes)
+    table = rng.integers(0, 256, (TABLE_K, block_bytes), dtype=np.uint8)
+    table[3, :block_bytes // 2] = 0
+    table[6] = table[5]
+    table[6, -1] ^= 0x80
+    assert len({bytes(b) for b in table}) == TABLE_K
+    objs = []
+    for j in range(5):
+        a = np.concatenate([table[np.roll(TABLE_SEQ, -j)].reshape(-1), table[1, :TABLE_TAIL]])
+        a.setflags(write=False)
+        objs.append(a)
+    return objs
+
+
+@pytest.mark.parametrize("waves", [1, 2, 4])
+@pytest.mark.parametrize("block_bytes", ODD_BB)
+def test_odd_block_tables(S, torch, wave_ctx, block_bytes, waves):
+    ctx = wave_ctx[waves]
+    objs = table_objects(block_bytes)
+    one, size, nb = objs[0], objs[0].size, len(TABLE_SEQ) + 1
+    assert size == len(TABLE_SEQ) * block_bytes + TABLE_TAIL
+    want = expect(S, [one], block_bytes)
+    # the closed form first: every table block occurs, the tail is a block of its own
+    assert (want.bytes, want.blocks, want.unique_blocks) == (size, nb, TABLE_K + 1)
+    t = dev(torch, one)
+    whole = ctx.measure(t, block_bytes=block_bytes)
+    assert whole == want
+    cuts = [0, 1, 2, nb // 2, nb + 5]
+    with ctx.measurer(block_bytes) as m:
+        for lo, hi in zip(cuts, cuts[1:]):
+            m.add_range(t[lo * block_bytes:], size, lo, hi)
+        m.add_range(t, size, 3, 3)             # empty ranges add nothing
+        m.add_range(t, size, nb, nb + 1)
+        assert m.result() == want
+    with ctx.measurer(block_bytes) as m:      # the object twice in one handle
+        m.add(t)
+        m.add(t)
+        r2 = m.result()
+    assert (r2.bytes, r2.zero_bytes, r2.blocks) == (2 * want.bytes, 2 * want.zero_bytes, 2 * want.blocks)
+    assert r2.unique_blocks == want.unique_blocks
+    # five objects, the sequence rotated from one to the next: the same blocks at other places
+    stride = -(-(size + 4096 + 12) // 16) * 16
+    wants = expect(S, objs, block_bytes)
+    assert (wants.bytes, wants.blocks, wants.unique_blocks) == (5 * size, 5 * nb, TABLE_K + 1)
+    assert wants.zero_bytes == 5 * want.zero_bytes
+    for p in (0x00, 0xA5):
+        got = ctx.measure_stream(dev(torch, strided(objs, stride, p)), size, 5, stride, block_bytes=block_bytes)
+        assert got == wants, hex(p)
+
+
+@pytest.mark.parametrize("block_bytes", ODD_BB)
+def test_odd_block_generated(S, torch, gpu_ctx, exp, dgen_dev, block_bytes):
+    a = exp.dgen(8 * MiB + 5, 2, 2)
+    want = expect(S, [a], block_bytes, hist=True)
+    assert want.blocks == -(-a.size // block_bytes)
+    assert gpu_ctx.measure(dgen_dev(8 * MiB + 5, 2, 2), block_bytes=block_bytes, hist=True) == want
+    b = exp.controlled(3 * MiB + 4097, 3, 2)
+    want = expect(S, [b], block_bytes)
+    assert want.blocks == -(-b.size // block_bytes)
+    assert gpu_ctx.measure(dev(torch, b), block_bytes=block_bytes) == want
+
+
+@pytest.mark.parametrize("waves", [1, 2, 4])
+@pytest.mark.parametrize("block_bytes", [12288, 69632])
+def test_odd_block_edge_sizes(S, torch, wave_ctx, block_bytes, waves):
+    ctx = wave_ctx[waves]
+    bb = block_bytes
+    rng = np.random.default_rng(4100 + bb)
+    for size in (1, bb - 16, bb - 1, bb, bb + 1, bb + 4096, 2 * bb + 4097, 3 * bb + 2080):
+        a = rng.integers(0, 256, size, dtype=np.uint8)
+        want = expect(S, [a], bb)
+        assert (want.bytes, want.blocks, want.unique_blocks) == (size, -(-size // bb), -(-size // bb)), size
+        assert ctx.measure(dev(torch, a), block_bytes=bb) == want, size
+
+
+# ---- 10. every piece enters the fingerprint, under a key of its own ---------------------------------
+
+def piece_set(block_bytes):
+    """The pieces that get a variant: all of a small block, granules 0, 8 and 16 of a 17-granule one."""
+    if block_bytes <= 12288:
+        return list(range(block_bytes // 16))
+    return [256 * g + k for g in (0, 8, 16) for k in range(256)]
+
+
+def distinct_piece_block(block_bytes, seed):
+    """A random block with no two equal 16-byte pieces, so that no exchange of two is a no-op."""
+    P = block_bytes // 16
+    while True:
+        a = np.random.default_rng(seed).integers(0, 256, block_bytes, dtype=np.uint8)
+        if len({bytes(x) for x in a.reshape(P, 16)}) == P:
+            return a
+        seed += 1
+
+
+def flipped(a, pieces):
+    """One copy of `a` per piece p, bit p % 128 of that piece flipped."""
+    out = np.tile(a, (len(pieces), 1))
+    for i, p in enumerate(pieces):
+        bit = p % 128
+        out[i, 16 * p + bit // 8] ^= 1 << (bit % 8)
+    return out
+
+
+def swapped(a, pieces):
+    """One copy of `a` per piece p and index bit b clear in p with q = p | 1 << b inside the block,
+    pieces p and q exchanged: any two pieces whose indices differ in one bit."""
+    P = a.size // 16
+    pairs = [(p, p | (1 << b)) for p in pieces for b in range(P.bit_length())
+             if not p >> b & 1 and p | (1 << b) < P]
+    out = np.tile(a, (len(pairs), 1))
+    for i, (p, q) in enumerate(pairs):
+        out[i, 16 * p:16 * p + 16] = a[16 * q:16 * q + 16]
+        out[i, 16 * q:16 * q + 16] = a[16 * p:16 * p + 16]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def piece_case(S, block_bytes):
+    """[a] + the flips + the swaps + [a] as one buffer, with its expected result, built once and
+    shared by the wave counts: 256 + 1024 variants (5.3 MB) at 4096, 768 + 3584 (53.5 MB) at 12288,
+    768 + 5120 (410 MB) at 69632."""
+    a = distinct_piece_block(block_bytes, 5000 + block_bytes)
+    P = block_bytes // 16
+    assert len({bytes(x) for x in a.reshape(P, 16)}) == P
+    pieces = piece_set(block_bytes)
+    buf = np.concatenate([a[None], flipped(a, pieces), swapped(a, pieces), a[None]]).reshape(-1)
+    buf.setflags(write=False)
+    return buf, expect(S, [buf], block_bytes)
+
+
+@pytest.mark.parametrize("waves", [1, 2, 4])
+@pytest.mark.parametrize("block_bytes", [4096, 12288, 69632])
+def test_every_piece_and_key(S, torch, wave_ctx, block_bytes, waves):
+    buf, want = piece_case(S, block_bytes)
+    assert want.blocks == buf.size // block_bytes > 2 * len(piece_set(block_bytes))
+    assert want.unique_blocks == want.blocks - 1      # numpy: every variant differs from `a` and from the others
+    t = dev(torch, buf)
+    got = wave_ctx[waves].measure(t, block_bytes=block_bytes)
+    del t
+    assert got == want
+
+
+@pytest.mark.parametrize("waves", [1, 2, 4])
+def test_every_piece_stream(S, torch, wave_ctx, waves):
+    """The flips at 12288 as objects of their own, each with the same 100-byte tail."""
+    bb = 12288
+    a = distinct_piece_block(bb, 5000 + bb)
+    rng = np.random.default_rng(5100)
+    tail = rng.integers(0, 256, 100, dtype=np.uint8)
+    blocks = np.concatenate([a[None], flipped(a, piece_set(bb)), a[None]])
+    objs = [np.concatenate([b, tail]) for b in blocks]
+    size, stride = bb + 100, bb + 112
+    want = expect(S, objs, bb)
+    assert (want.blocks, want.unique_blocks) == (2 * len(objs), bb // 16 + 1 + 1)   # the flips, `a`, the tail
+    got = wave_ctx[waves].measure_stream(dev(torch, strided(objs, stride, 0xA5)), size, len(objs), stride,
+                                         block_bytes=bb)
+    assert got == want
+
+
+# ---- 11. the largest blocks ----------------------------------------------------------------------------
+# Zeroed device buffers with marker bytes, as in test_object_across_granule_split: the expected
+# numbers follow from where the markers are.
+
+def test_block_of_one_gib(S, torch, gpu_ctx):
+    """block_bytes = 2^30: gpb = 262144, piece indices up to 2^26, 4096 laps per lane in pass 2."""
+    bb = 1 << 30
+    n = 2 * bb + 100
+    t = torch.zeros(n + 12, dtype=torch.uint8, device="cuda:0")
+    t[bb - 1] = 7
+    t[2 * bb - 1] = 7
+    hist = [0] * 256
+    hist[0], hist[7] = n - 2, 2
+    r = gpu_ctx.measure(t, nbytes=n, block_bytes=bb, hist=True)
+    assert r == S.MeasureResult(n, n - 2, 3, 2, tuple(hist))     # two equal blocks and the 100-byte tail
+    t[2 * bb - 1] = 0
+    t[2 * bb - 2] = 7                                            # the last piece of block 1, one byte down
+    r = gpu_ctx.measure(t, nbytes=n, block_bytes=bb, hist=True)
+    assert r == S.MeasureResult(n, n - 2, 3, 3, tuple(hist))
+    del t
+    torch.cuda.empty_cache()
+
+
+def test_block_of_one_gib_less_a_granule(S, torch, gpu_ctx):
+    """block_bytes = 2^30 - 4096: gpb = 262143, odd, on the one-wave-per-block kernel."""
+    bb = (1 << 30) - 4096
+    n = 1 << 31
+    t = torch.zeros(n, dtype=torch.uint8, device="cuda:0")
+    t[bb - 1] = 7
+    t[2 * bb - 1] = 7
+    r = gpu_ctx.measure(t, nbytes=n, block_bytes=bb)
+    assert n - 2 * bb == 8192
+    assert r == S.MeasureResult(n, n - 2, 3, 2)                  # two equal blocks and 8192 zeros
+    t[2 * bb - 1] = 0
+    t[2 * bb - 4097] = 7                                         # the same byte one granule down
+    r = gpu_ctx.measure(t, nbytes=n, block_bytes=bb)
+    assert r == S.MeasureResult(n, n - 2, 3, 3)
+    del t
+    torch.cuda.empty_cache()
+
+
+# ---- 12. host buffers across the chunking ----------------------------------------------------------------
+
+@pytest.mark.parametrize("hist", [False, True])
+def test_measure_data_chunk_of_odd_blocks(S, exp, hist):
+    """12288-byte blocks: a chunk is 5461 whole blocks (67 104 768 bytes, not 64 MiB); the same
+    block on both sides of the chunk edge."""
+    bb = 12288
+    per = HOST_CHUNK // bb
+    assert (per, per * bb) == (5461, 67104768)
+    size = (per + 2) * bb + 100
+    a = exp.dgen(size, 2, 2).copy()
+    same = np.random.default_rng(6000).integers(0, 256, bb, dtype=np.uint8)
+    a[(per - 1) * bb:per * bb] = same
+    a[per * bb:(per + 1) * bb] = same
+    want = expect(S, [a], bb, hist=hist)
+    assert (want.bytes, want.blocks) == (size, per + 3)         # the 100-byte tail is the last one
+    assert S.measure_data(a, block_bytes=bb, hist=hist) == want
+    if not hist:   # apart, the two blocks are one block more: the pair was counted once across the edge
+        a[per * bb] ^= 1
+        apart = expect(S, [a], bb)
+        assert apart.unique_blocks == want.unique_blocks + 1
+        assert S.measure_data(a, block_bytes=bb) == apart
+
+
+OWN_BB = HOST_CHUNK + 4096
+OWN_RUNS = ((0, 4096), (HOST_CHUNK - 16, HOST_CHUNK + 16), (OWN_BB - 16, OWN_BB))
+
+
+def own_block(seed):
+    """A block larger than the staging chunk: zeros, with non-zero random bytes at its start,
+    around offset 64 MiB and at its end."""
+    rng = np.random.default_rng(seed)
+    b = np.zeros(OWN_BB, np.uint8)
+    for lo, hi in OWN_RUNS:
+        b[lo:hi] = rng.integers(1, 256, hi - lo, dtype=np.uint8)
+    return b
+
+
+@pytest.mark.parametrize("case", ["short", "exact", "copy", "changed"])
+def test_measure_data_blocks_above_the_chunk(S, case):
+    """block_bytes = 64 MiB + 4096: the call stages through two device buffers of its own."""
+    b = own_block(6100)
+    nonzero = sum(hi - lo for lo, hi in OWN_RUNS)
+    if case == "short":
+        a, shape = b[:OWN_BB - 100], (1, 1, OWN_BB - 100 - (nonzero - 16))
+    elif case == "exact":
+        a, shape = b, (1, 1, OWN_BB - nonzero)
+    else:
+        a = np.concatenate([b, b, b[:4196]])
+        shape = (3, 2, a.size - 2 * nonzero - 4096)
+        if case == "changed":
+            k = OWN_BB + HOST_CHUNK + 5                          # inside block 1's run around 64 MiB
+            a[k] = a[k] % 255 + 1                                # another non-zero value
+            shape = (3, 3, shape[2])
+    want = expect(S, [a], OWN_BB, hist=True)
+    assert (want.blocks, want.unique_blocks, want.zero_bytes) == shape
+    assert S.measure_data(a, block_bytes=OWN_BB, hist=True) == want
