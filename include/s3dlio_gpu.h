@@ -379,6 +379,92 @@ int s3dg_measure_get(s3dg_measure *m, s3dg_measure_result *out);
 int s3dg_measure_data(const uint8_t *buf, uint64_t len, uint64_t block_bytes, int flags,
                       s3dg_measure_result *out);
 
+/* ---- content-defined chunking (read-only) -----------------
+ * What a payload is worth to a store that deduplicates content-defined
+ * chunks (backup targets, most deduplicating object stores): a rolling hash
+ * over a 32-byte window picks the cut points between min_bytes and max_bytes,
+ * so equal content is found at any byte offset.  The fixed-block measure above
+ * cannot answer for such a store.
+ *
+ * Every object is chunked on its own, from its first byte; no window reaches
+ * outside the object.  With G[b] = lowbias32(b + 0x9E3779B9) and bits =
+ * log2(avg_bytes), position i >= 31 of an object is a candidate cut when
+ * h_i = sum over k in [0, 32) of G[byte[i - k]] << k (mod 2^32) has its top
+ * `bits` bits zero.  A chunk that starts at s ends at the first candidate
+ * e >= s + min_bytes - 1 if that makes it at most max_bytes long; otherwise it
+ * is cut at max_bytes (a forced cut); the object's end closes the last chunk
+ * at whatever length it has (not a forced cut, unless the chunk has exactly
+ * max_bytes and does not end on a candidate).  min_bytes == max_bytes is
+ * fixed blocks.  Chunks are compared through the measure's 128-bit
+ * fingerprints (the pieces counted from the chunk's first byte, the length
+ * folded in), so a chunk with the bytes of a block has that block's
+ * fingerprint; unique_chunks is the exact number of distinct fingerprints.
+ *
+ * avg_bytes: a power of two from 64 to 2^24; 32 <= min_bytes <= max_bytes <=
+ * 2^30; neither need be a multiple of anything.  Usual values: 2048 / 8192 /
+ * 65536.
+ *
+ * A handle accumulates over adds on any stream, so objects that pass through
+ * a ring in several launches count as one payload.  Out of scope: block
+ * ranges of one object across adds (the walk's state, the start of the open
+ * chunk and its partial fingerprint, would have to be carried between them);
+ * every add holds whole objects.
+ *
+ * Device memory.  Per add and stream, as scratch that is reused: the
+ * candidate bitmap, 1/8 of the add's bytes (and 4 bytes per 4 KiB for the
+ * candidate counts), and 12 bytes of (offset, length) per record slot, ceil(obj_size / min_bytes) + 1 slots per object.  In the
+ * handle: 20 bytes (fingerprint and length) per record slot of every add, in
+ * arrays that grow by doubling, plus, while s3dg_chunks_get runs, 24 bytes of
+ * sort keys and indices per slot and hipCUB's radix-sort scratch.  Slots are
+ * reserved for the most chunks an object can have, so a handle holds at most
+ * 2^31 - 1 of them: about 4 TiB of payload at min_bytes 2048, 64 GiB at 32.
+ * Growing the arrays waits for the adds the handle has enqueued.  One wave
+ * walks each object's cuts and one wave fingerprints each chunk, so the passes
+ * are parallel over objects and chunks, not inside one.
+ * Destroy a handle before its context. */
+typedef struct s3dg_chunks s3dg_chunks;
+typedef struct {
+    uint64_t bytes;          /* payload bytes chunked (stride gaps excluded) */
+    uint64_t chunks;         /* chunks cut, every object's last one included */
+    uint64_t unique_chunks;  /* distinct among them (bytes and length) */
+    uint64_t unique_bytes;   /* summed length of one chunk per distinct fingerprint */
+    uint64_t candidates;     /* positions whose window hash passes */
+    uint64_t forced_cuts;    /* chunks cut at max_bytes without a candidate */
+} s3dg_chunk_result;
+int s3dg_chunks_create(s3dg_ctx *ctx, uint64_t min_bytes, uint64_t avg_bytes, uint64_t max_bytes,
+                       s3dg_chunks **out);
+int s3dg_chunks_destroy(s3dg_chunks *h);
+int s3dg_chunks_reset(s3dg_chunks *h);   /* waits for the enqueued adds; an empty handle again */
+/* n_objs objects of obj_size bytes at src + j*stride (device memory; the
+ * refusals of s3dg_measure_add_stream).  Asynchronous on `stream` and ordered
+ * like a fill: a later launch on the same stream may overwrite src.  Stride
+ * gaps, the bytes before src and whatever follows the last object are never
+ * read.  Slots and scratch are reserved on the host at call time, so adds from
+ * several threads on several streams are safe.  A zero-length add launches
+ * nothing. */
+int s3dg_chunks_add_stream(s3dg_chunks *h, const void *src, uint64_t obj_size, uint64_t stride,
+                           uint64_t n_objs, void *stream);
+/* Waits for the enqueued adds, counts the distinct fingerprints on a copy and
+ * fills *out.  The handle is unchanged: get again, or add and get.  An empty
+ * handle yields all zeros. */
+int s3dg_chunks_get(s3dg_chunks *h, s3dg_chunk_result *out);
+/* Diagnostics.  S3DG_CHUNKS_TIME_PASSES (0 / 1, default 0): HIP events around
+ * the three passes of every following add; s3dg_chunks_pass_seconds waits for
+ * the latest such add and writes its candidate, cut and fingerprint pass times
+ * to seconds[0..2].  S3DG_CHUNKS_GEAR_TABLE (0 / 1, default 1): the candidate
+ * pass reads G from 256 words of LDS or computes it per byte; results are
+ * identical. */
+enum { S3DG_CHUNKS_TIME_PASSES = 1, S3DG_CHUNKS_GEAR_TABLE = 2 };
+int s3dg_chunks_set_option(s3dg_chunks *h, int option, int value);
+int s3dg_chunks_pass_seconds(s3dg_chunks *h, double *seconds);
+/* A host buffer (any alignment, read-only memory included) as one object, on
+ * a host slot's GPU.  Windows and chunks cross any copy's edge, so the whole
+ * buffer is staged in device memory (len rounded up to 16 bytes, copied 64 MiB
+ * at a time); a buffer that does not fit is an error with hipMalloc's text.
+ * len == 0: all zeros, no GPU needed. */
+int s3dg_chunk_data(const uint8_t *buf, uint64_t len, uint64_t min_bytes, uint64_t avg_bytes,
+                    uint64_t max_bytes, s3dg_chunk_result *out);
+
 /* ---- memory / copy helpers ------------------------------------------------ */
 int s3dg_device_alloc(s3dg_ctx *ctx, uint64_t bytes, void **out);
 int s3dg_device_free(s3dg_ctx *ctx, void *p);

@@ -59,6 +59,12 @@ class MeasureRec(ctypes.Structure):
                 ("hist", c_u64 * 256)]
 
 
+class ChunkRec(ctypes.Structure):
+    """s3dg_chunk_result"""
+    _fields_ = [("bytes", c_u64), ("chunks", c_u64), ("unique_chunks", c_u64), ("unique_bytes", c_u64),
+                ("candidates", c_u64), ("forced_cuts", c_u64)]
+
+
 # name -> (restype, argtypes); the exact export list of include/s3dlio_gpu.h
 SIGNATURES = {
     "s3dg_ctx_create": (c_int, [c_int, ctypes.POINTER(c_vp)]),
@@ -115,6 +121,14 @@ SIGNATURES = {
     "s3dg_measure_add_range": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp]),
     "s3dg_measure_get": (c_int, [c_vp, ctypes.POINTER(MeasureRec)]),
     "s3dg_measure_data": (c_int, [c_vp, c_u64, c_u64, c_int, ctypes.POINTER(MeasureRec)]),
+    "s3dg_chunks_create": (c_int, [c_vp, c_u64, c_u64, c_u64, ctypes.POINTER(c_vp)]),
+    "s3dg_chunks_destroy": (c_int, [c_vp]),
+    "s3dg_chunks_reset": (c_int, [c_vp]),
+    "s3dg_chunks_add_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp]),
+    "s3dg_chunks_get": (c_int, [c_vp, ctypes.POINTER(ChunkRec)]),
+    "s3dg_chunks_set_option": (c_int, [c_vp, c_int, c_int]),
+    "s3dg_chunks_pass_seconds": (c_int, [c_vp, ctypes.POINTER(ctypes.c_double)]),
+    "s3dg_chunk_data": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, ctypes.POINTER(ChunkRec)]),
     "s3dg_write_ceiling": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
     "s3dg_write_ceiling_tiled": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
     "s3dg_write_ceiling_fill": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),

@@ -113,6 +113,40 @@ class MeasureResult:
                    tuple(int(v) for v in r.hist) if hist else None)
 
 
+@dataclass(frozen=True)
+class ChunkResult:
+    """s3dg_chunk_result: what a payload looks like to a store that
+    deduplicates content-defined chunks."""
+    bytes: int = 0            # payload bytes chunked (stride gaps excluded)
+    chunks: int = 0           # chunks cut, every object's last one included
+    unique_chunks: int = 0    # distinct among them (bytes and length)
+    unique_bytes: int = 0     # summed length of one chunk per distinct fingerprint
+    candidates: int = 0       # positions whose window hash passes
+    forced_cuts: int = 0      # chunks cut at max_bytes without a candidate
+
+    @property
+    def dedup_ratio(self) -> float:
+        """bytes / unique_bytes: what a dedup engine with this chunking saves (n : 1)."""
+        return self.bytes / self.unique_bytes if self.unique_bytes else 0.0
+
+    @property
+    def unique_fraction(self) -> float:
+        return self.unique_chunks / self.chunks if self.chunks else 0.0
+
+    @property
+    def mean_chunk(self) -> float:
+        return self.bytes / self.chunks if self.chunks else 0.0
+
+    @classmethod
+    def _of(cls, r) -> "ChunkResult":
+        return cls(int(r.bytes), int(r.chunks), int(r.unique_chunks), int(r.unique_bytes), int(r.candidates),
+                   int(r.forced_cuts))
+
+
+CHUNK_DEFAULTS = (2048, 8192, 65536)   # min_bytes, avg_bytes, max_bytes
+_CHUNKS_TIME_PASSES, _CHUNKS_GEAR_TABLE = 1, 2   # S3DG_CHUNKS_* options
+
+
 def _ptr(x) -> int:
     """Device pointer of a torch CUDA tensor (contiguous) or a raw int."""
     if isinstance(x, int):
@@ -512,6 +546,32 @@ class Context:
             m.add_stream(src, obj_size, n_objs, stride, stream=stream)
             return m.result()
 
+    # -- content-defined chunking (read-only) ------------------------------------
+    # How much of a payload is distinct to a store that cuts chunks where a
+    # rolling hash over 32 bytes says so, between min_bytes and max_bytes
+    # (avg_bytes: a power of two).  Every object is chunked on
+    # its own from its first byte.
+    def chunker(self, min_bytes: int = CHUNK_DEFAULTS[0], avg_bytes: int = CHUNK_DEFAULTS[1],
+                max_bytes: int = CHUNK_DEFAULTS[2]) -> "Chunker":
+        """An accumulating handle: add / add_stream on any stream, then result()."""
+        return Chunker(self, min_bytes, avg_bytes, max_bytes)
+
+    def measure_chunks(self, src, nbytes: int | None = None, min_bytes: int = CHUNK_DEFAULTS[0],
+                       avg_bytes: int = CHUNK_DEFAULTS[1], max_bytes: int = CHUNK_DEFAULTS[2],
+                       stream=None) -> ChunkResult:
+        """One object of `nbytes` at src."""
+        with self.chunker(min_bytes, avg_bytes, max_bytes) as h:
+            h.add(src, nbytes, stream=stream)
+            return h.result()
+
+    def measure_chunks_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None,
+                              min_bytes: int = CHUNK_DEFAULTS[0], avg_bytes: int = CHUNK_DEFAULTS[1],
+                              max_bytes: int = CHUNK_DEFAULTS[2], stream=None) -> ChunkResult:
+        """n_objs equal objects as fill_stream lays them out; stride gaps are never read."""
+        with self.chunker(min_bytes, avg_bytes, max_bytes) as h:
+            h.add_stream(src, obj_size, n_objs, stride, stream=stream)
+            return h.result()
+
     def write_ceiling(self, dst, nbytes: int | None = None, pattern: int = 0xA5A5A5A5,
                       stream=None) -> None:
         n = _nbytes(dst) if nbytes is None else int(nbytes)
@@ -590,6 +650,72 @@ class Measure:
     def close(self) -> None:
         if getattr(self, "_h", None):
             call("s3dg_measure_destroy", self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Chunker:
+    """s3dg_chunks: a content-defined chunking analysis that accumulates over
+    calls and streams (Context.chunker).  The adds are asynchronous on their
+    stream and ordered like a fill; every add holds whole objects.  result()
+    waits for them and leaves the handle unchanged."""
+
+    def __init__(self, ctx: Context, min_bytes: int = CHUNK_DEFAULTS[0], avg_bytes: int = CHUNK_DEFAULTS[1],
+                 max_bytes: int = CHUNK_DEFAULTS[2]):
+        self._ctx = ctx
+        self.min_bytes, self.avg_bytes, self.max_bytes = int(min_bytes), int(avg_bytes), int(max_bytes)
+        h = c_vp()
+        call("s3dg_chunks_create", ctx._h, self.min_bytes, self.avg_bytes, self.max_bytes, ctypes.byref(h))
+        self._h = h
+
+    def add(self, src, nbytes: int | None = None, stream=None) -> None:
+        """One object of `nbytes` at src."""
+        n = _nbytes(src) if nbytes is None else int(nbytes)
+        self.add_stream(src, n, 1, stride=0, stream=stream)   # one object: no stride to align
+
+    def add_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None, stream=None) -> None:
+        """n_objs objects of obj_size bytes, object j at src + j*stride."""
+        stride = obj_size if stride is None else stride
+        need = (int(n_objs) - 1) * int(stride) + int(obj_size) if n_objs > 0 and obj_size > 0 else 0
+        call("s3dg_chunks_add_stream", self._h, self._ctx._src(src, need), int(obj_size), int(stride),
+             int(n_objs), self._ctx._s(stream))
+
+    def result(self) -> ChunkResult:
+        r = _lib.ChunkRec()
+        call("s3dg_chunks_get", self._h, ctypes.byref(r))
+        return ChunkResult._of(r)
+
+    def reset(self) -> None:
+        call("s3dg_chunks_reset", self._h)
+
+    def time_passes(self, on: bool = True) -> None:
+        """HIP events around the three passes of every following add (pass_seconds)."""
+        call("s3dg_chunks_set_option", self._h, _CHUNKS_TIME_PASSES, 1 if on else 0)
+
+    def gear_table(self, on: bool = True) -> None:
+        """The candidate pass's G from LDS (default) or computed per byte; same results."""
+        call("s3dg_chunks_set_option", self._h, _CHUNKS_GEAR_TABLE, 1 if on else 0)
+
+    def pass_seconds(self) -> tuple[float, float, float]:
+        """Candidate, cut and fingerprint pass times of the latest timed add (waits for it)."""
+        t = (ctypes.c_double * 3)()
+        call("s3dg_chunks_pass_seconds", self._h, t)
+        return float(t[0]), float(t[1]), float(t[2])
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            call("s3dg_chunks_destroy", self._h)
             self._h = None
 
     def __enter__(self):

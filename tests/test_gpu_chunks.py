@@ -1,0 +1,546 @@
+"""GPU: a payload's dedup under content-defined chunking (k_chunk_candidates,
+k_chunk_cuts, k_chunk_fp, the distinct count and the surfaces over them;
+DESIGN.md §5.11).
+
+The judge is a numpy restatement of the definition, written here from the
+document: G, the 32-byte window sums (vectorised), the cut rule (a Python loop
+over the cuts), and `bytes` of every chunk in a dict for the distinct counts,
+never a restatement of the fingerprint.  Every field is compared exactly.
+"""
+import functools
+import threading
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+MiB = 1 << 20
+DEFAULTS = (2048, 8192, 65536)
+SMALL = (32, 64, 256)
+PARAMS = [SMALL, (64, 256, 1024), (100, 128, 1000), DEFAULTS]
+SIZES = [1, 31, 32, 33, 63, 64, 255, 256, 257, 4095, 4096, 4097, 65613, MiB + 5]
+EVENTS = {"cut_at_min", "skipped_before_min", "candidate_at_max", "forced", "forced_then_candidate"}
+
+
+# ---- the definition, restated ----------------------------------------------------
+
+def _gear():
+    x = (np.arange(256, dtype=np.uint64) + 0x9E3779B9) & 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & 0xFFFFFFFF
+    x ^= x >> 16
+    return x.astype(np.uint32)
+
+
+G = _gear()
+
+
+def window_hash(rows):
+    """h_i for i >= 31 of every row (one object per row): shape (n, len - 31)."""
+    g = G[rows]
+    m = rows.shape[1] - 31
+    h = np.zeros((rows.shape[0], m), np.uint32)
+    for k in range(32):
+        h += g[:, 31 - k:31 - k + m] << np.uint32(k)
+    return h
+
+
+def candidates(rows, bits):
+    """Candidate cuts of equal-length objects, one per row."""
+    rows = np.atleast_2d(np.ascontiguousarray(rows, np.uint8))
+    n = rows.shape[1]
+    cand = np.zeros(rows.shape, bool)
+    step = max(1, (1 << 22) // rows.shape[0])
+    for lo in range(31, n, step):
+        hi = min(n, lo + step)
+        cand[:, lo:hi] = (window_hash(rows[:, lo - 31:hi]) >> np.uint32(32 - bits)) == 0
+    return cand
+
+
+def cuts_of(cand, mn, mx):
+    """The chunks [s, e] of one object, its forced cuts and the events of the cut rule met."""
+    n = cand.size
+    pos = np.flatnonzero(cand)
+    out, forced, ev = [], 0, set()
+    s = 0
+    while s < n:
+        lo = s + mn - 1
+        if lo >= n:
+            e = n - 1                                   # the object's end closes the last chunk
+        else:
+            if lo - 1 >= s and cand[lo - 1]:
+                ev.add("skipped_before_min")
+            k = int(np.searchsorted(pos, lo))
+            c = int(pos[k]) if k < pos.size else None   # the smallest candidate >= s + min - 1
+            if c is not None and c - s + 1 <= mx:
+                e = c
+                if e == lo:
+                    ev.add("cut_at_min")
+                if e == s + mx - 1:
+                    ev.add("candidate_at_max")
+            elif s + mx <= n:
+                e = s + mx - 1                          # cut at max_bytes
+                forced += 1
+                ev.add("forced")
+                if e + 1 < n and cand[e + 1]:
+                    ev.add("forced_then_candidate")
+            else:
+                e = n - 1
+        out.append((s, e))
+        s = e + 1
+    return out, forced, ev
+
+
+def restate(S, objs, params, events=None):
+    """The result of chunking the objects (host arrays) in one handle."""
+    mn, avg, mx = params
+    bits = avg.bit_length() - 1
+    seen = {}
+    nbytes = chunks = ncand = forced = 0
+    by_len = {}
+    for a in objs:
+        by_len.setdefault(len(a), []).append(np.ascontiguousarray(a, np.uint8))
+    for n, group in by_len.items():
+        rows = np.stack(group)
+        cand = candidates(rows, bits)
+        ncand += int(cand.sum())
+        for a, c in zip(group, cand):
+            out, f, ev = cuts_of(c, mn, mx)
+            mv = memoryview(a)
+            for s, e in out:
+                seen[bytes(mv[s:e + 1])] = e - s + 1
+            chunks += len(out)
+            forced += f
+            nbytes += n
+            if events is not None:
+                events |= ev
+    return S.ChunkResult(nbytes, chunks, len(seen), sum(seen.values()), ncand, forced)
+
+
+# ---- fixtures -----------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def S():
+    import s3dlio_amd
+    return s3dlio_amd
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch
+    return torch
+
+
+def dev(torch, a):
+    return torch.from_numpy(np.array(a, dtype=np.uint8, copy=True)).to("cuda:0")
+
+
+def strided(objs, stride, poison):
+    """The objects at a stride, the gaps (and the space after the last one) filled with `poison`."""
+    buf = np.full(stride * len(objs), poison, np.uint8)
+    for j, o in enumerate(objs):
+        buf[j * stride:j * stride + len(o)] = o
+    return buf
+
+
+@functools.lru_cache(maxsize=None)
+def random_bytes(size, seed=1):
+    a = np.random.default_rng(seed).integers(0, 256, size, dtype=np.uint8)
+    a.setflags(write=False)
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def window13():
+    """A 32-byte string whose window hash passes at bits = 13 (found by search on the CPU)."""
+    rng = np.random.default_rng(13)
+    while True:
+        rows = rng.integers(1, 256, (1 << 16, 32), dtype=np.uint8)
+        hit = np.flatnonzero((window_hash(rows)[:, 0] >> np.uint32(19)) == 0)
+        if hit.size:
+            w = rows[hit[0]].copy()
+            w.setflags(write=False)
+            return w
+
+
+def zeros_with(size, ends, w):
+    """Zeros with the string w placed so that it ends at each offset of `ends` (its
+    head cut off where it would start before the object)."""
+    a = np.zeros(size, np.uint8)
+    for e in ends:
+        lo = e - 31
+        a[max(lo, 0):e + 1] = w[max(-lo, 0):]
+    return a
+
+
+# ---- 1. random bytes --------------------------------------------------------------------
+
+@pytest.mark.parametrize("params", PARAMS, ids=str)
+def test_random_bytes(S, torch, gpu_ctx, params):
+    events = set()
+    for size in SIZES:
+        a = random_bytes(size)
+        t = dev(torch, np.concatenate([a, np.full(16, 0xEE, np.uint8)]))
+        got = gpu_ctx.measure_chunks(t, size, *params)
+        want = restate(S, [a], params, events)
+        assert got == want, size
+        assert got.unique_bytes == size                     # random chunks of >= 32 bytes never repeat
+    if params == SMALL:
+        assert events == EVENTS, EVENTS - events            # every event of the cut rule was met
+
+
+def test_gear_table_or_arithmetic(S, torch, gpu_ctx):
+    """The candidate pass with G from LDS and with G computed: the same result."""
+    a = random_bytes(MiB + 5)
+    t = dev(torch, a)
+    want = restate(S, [a], SMALL)
+    for table in (True, False):
+        with gpu_ctx.chunker(*SMALL) as h:
+            h.gear_table(table)
+            h.add(t)
+            assert h.result() == want, table
+
+
+# ---- 2. crafted windows -----------------------------------------------------------------
+
+def test_window_at_every_granule_and_lane_edge(S, torch, gpu_ctx):
+    """The window ends at every offset from 4064 to 4128 of a zero background: the
+    granule's edge, both sides of it, and every lane-run edge near it."""
+    w = window13()
+    size, stride = 3 * 4096 + 77, 3 * 4096 + 96
+    ends = list(range(4064, 4129))
+    objs = [zeros_with(size, [e], w) for e in ends]
+    got = gpu_ctx.measure_chunks_stream(dev(torch, strided(objs, stride, 0x5A)), size, len(objs), stride)
+    assert got == restate(S, objs, DEFAULTS)
+    for e, o in zip(ends, objs):                           # one by one: a miss names its offset
+        r = gpu_ctx.measure_chunks(dev(torch, np.concatenate([o, np.full(19, 0x5A, np.uint8)])), size)
+        assert r == restate(S, [o], DEFAULTS), e
+        assert r.candidates >= 1 and r.chunks == 2 and r.forced_cuts == 0
+
+
+@pytest.mark.parametrize("mn,mx,first", [(2048, 65536, 5000), (2048, 65536, None), (32, 256, None), (100, 1000, 777)],
+                         ids=str)
+def test_window_against_min_and_max(S, torch, gpu_ctx, mn, mx, first):
+    """The window ends at s + min - 2, s + min - 1, s + max - 1 and s + max, s the
+    start of the object or the byte after an earlier cut at `first`.  With min = 32
+    at the object's start these are offsets 30 and 31: one byte before the first
+    possible candidate, where the string is none, and the first possible candidate."""
+    w = window13()
+    params = (mn, 8192, mx)
+    s = 0 if first is None else first + 1
+    size = s + mx + 2 * mn + 77
+    objs = []
+    for d in (mn - 2, mn - 1, mx - 1, mx):
+        objs.append(zeros_with(size, ([] if first is None else [first]) + [s + d], w))
+    events = set()
+    want = [restate(S, [o], params, events) for o in objs]
+    for o, r in zip(objs, want):
+        got = gpu_ctx.measure_chunks(dev(torch, np.concatenate([o, np.full(16, 0xC3, np.uint8)])), size, *params)
+        assert got == r
+    assert events == EVENTS - ({"skipped_before_min"} if s + mn - 2 < 31 else set())
+
+
+# ---- 3. constant objects -------------------------------------------------------------------
+
+@pytest.mark.parametrize("params,size", [((100, 128, 1000), 12345), (DEFAULTS, 300001), (SMALL, 4097)], ids=str)
+def test_zeros_are_forced_cuts_only(S, torch, gpu_ctx, params, size):
+    z = np.zeros(size, np.uint8)
+    got = gpu_ctx.measure_chunks(dev(torch, z), size, *params)
+    assert got == restate(S, [z], params)
+    mx = params[2]
+    assert got == S.ChunkResult(size, size // mx + 1, 2, mx + size % mx, 0, size // mx)
+
+
+@pytest.mark.parametrize("mn,mx,size", [(100, 1000, 12345), (32, 256, 8191), (37, 37, 5000)], ids=str)
+def test_constant_candidate_byte_cuts_every_min(S, torch, gpu_ctx, mn, mx, size):
+    """Byte 57 is a candidate everywhere at bits = 6; byte 0 is not."""
+    a = np.full(size, 57, np.uint8)
+    got = gpu_ctx.measure_chunks(dev(torch, a), size, mn, 64, mx)
+    assert got == restate(S, [a], (mn, 64, mx))
+    assert got == S.ChunkResult(size, -(-size // mn), 2, mn + size % mn, size - 31, 0)
+    z = np.zeros(size, np.uint8)
+    assert gpu_ctx.measure_chunks(dev(torch, z), size, mn, 64, mx).candidates == 0
+
+
+# ---- 4. fixed blocks ------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def generated(S, torch, gpu_ctx):
+    """Payloads filled on the GPU (device tensor, host copy), made once."""
+    @functools.lru_cache(maxsize=None)
+    def get(kind, size, dedup, compress):
+        t = torch.empty(size + 16, dtype=torch.uint8, device="cuda:0")
+        t[size:] = 0xEE
+        if kind == "controlled":
+            gpu_ctx.fill_controlled(t, size, dedup=dedup, compress=compress, entropy=42)
+        elif kind == "dgen":
+            gpu_ctx.dgen_fill(t, size, dedup=dedup, compress=compress, seed=7)
+        else:
+            t[:size] = torch.from_numpy(np.array(random_bytes(size, 9))).to("cuda:0")
+        torch.cuda.synchronize()
+        a = t[:size].cpu().numpy()
+        a.setflags(write=False)
+        return t, a
+    return get
+
+
+@pytest.mark.parametrize("block", [4096, 12288])
+@pytest.mark.parametrize("kind,size,dedup,compress", [("random", 3 * MiB + 4097, 0, 0), ("controlled", 3 * MiB + 4097, 1, 1),
+                                                      ("controlled", 3 * MiB + 4097, 4, 2), ("dgen", 2 * MiB, 3, 2)],
+                         ids=str)
+def test_min_equal_max_is_fixed_blocks(S, torch, gpu_ctx, generated, block, kind, size, dedup, compress):
+    t, a = generated(kind, size, dedup, compress)
+    got = gpu_ctx.measure_chunks(t, size, block, 8192, block)
+    m = gpu_ctx.measure(t, size, block_bytes=block)
+    assert (got.chunks, got.unique_chunks, got.bytes) == (m.blocks, m.unique_blocks, m.bytes)
+    blocks = {bytes(a[o:o + block]) for o in range(0, size, block)}
+    assert got.unique_chunks == len(blocks) and got.unique_bytes == sum(len(b) for b in blocks)
+
+
+# ---- 5. generated payloads --------------------------------------------------------------------
+
+@pytest.mark.parametrize("params", [DEFAULTS, SMALL], ids=str)
+@pytest.mark.parametrize("kind,dedup,compress", [("controlled", d, c) for d in (1, 2, 4) for c in (1, 2, (3, 2))] +
+                         [("dgen", 3, 2)], ids=str)
+def test_generated_payloads(S, torch, gpu_ctx, generated, kind, dedup, compress, params):
+    size = 2 * MiB if kind == "dgen" else MiB + 4097
+    t, a = generated(kind, size, dedup, compress)
+    assert gpu_ctx.measure_chunks(t, size, *params) == restate(S, [a], params)
+
+
+# ---- 6. streams ---------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("params", [SMALL, DEFAULTS], ids=str)
+def test_ragged_stream_ignores_gaps(S, torch, gpu_ctx, params):
+    rng = np.random.default_rng(5)
+    size, stride = 70001, 70001 + 4096 + 15            # a 16-byte aligned stride with a > 4 KiB gap
+    objs = [rng.integers(0, 256, size, dtype=np.uint8) for _ in range(5)]
+    objs[3][:30000] = objs[1][:30000]                  # shared content between objects
+    objs[4] = objs[0].copy()                           # two byte-identical objects behind different gaps
+    want = restate(S, objs, params)
+    gaps = strided(objs, stride, 0)
+    gaps[size:stride] = 0x33                           # ... so that a window crossing into the object would differ
+    gaps[3 * stride + size:4 * stride] = 0x77
+    for buf in (strided(objs, stride, 0x00), strided(objs, stride, 0xA5), gaps):
+        assert gpu_ctx.measure_chunks_stream(dev(torch, buf), size, 5, stride, *params) == want
+    pair = gpu_ctx.measure_chunks_stream(dev(torch, strided([objs[0], objs[4]], stride, 0x99)), size, 2, stride,
+                                         *params)
+    assert pair.chunks == 2 * pair.unique_chunks and pair.bytes == 2 * pair.unique_bytes
+
+
+def test_tiny_objects(S, torch, gpu_ctx):
+    for v in (0, 57):
+        b = np.full(1, v, np.uint8)
+        r = gpu_ctx.measure_chunks(dev(torch, np.concatenate([b, np.full(15, 0xEE, np.uint8)])), 1, *SMALL)
+        assert r == restate(S, [b], SMALL) == S.ChunkResult(1, 1, 1, 1, 0, 0)
+    rng = np.random.default_rng(6)
+    objs = [rng.integers(0, 256, 100, dtype=np.uint8) for _ in range(7)]
+    objs[5] = objs[2].copy()
+    for params in (SMALL, DEFAULTS):
+        r = gpu_ctx.measure_chunks_stream(dev(torch, strided(objs, 112, 0x11)), 100, 7, 112, *params)
+        assert r == restate(S, objs, params)
+
+
+def test_stream_across_object_split(S, torch, gpu_ctx):
+    """More than 65 535 objects: pass A's launch is split along the objects."""
+    n = 65535 + 3
+    rows = np.random.default_rng(8).integers(0, 256, (n, 100), dtype=np.uint8)
+    rows[-1] = rows[65534]                             # the objects on both sides of the split, repeated
+    rows[-2] = rows[65535]
+    buf = np.full((n, 112), 0x42, np.uint8)
+    buf[:, :100] = rows
+    r = gpu_ctx.measure_chunks_stream(dev(torch, buf.reshape(-1)), 100, n, 112, *SMALL)
+    assert r == restate(S, list(rows), SMALL)
+    assert r.bytes == 100 * n and r.unique_chunks < r.chunks
+
+
+def test_stride_above_4_gib(S, torch, gpu_ctx):
+    """Two small objects at a stride above 4 GiB; the gap is never initialised."""
+    stride, size = (1 << 32) + 4096, 5003
+    a = random_bytes(size, 21)
+    b = a.copy()
+    b[2500] ^= 1
+    t = torch.empty(stride + size + 13, dtype=torch.uint8, device="cuda:0")
+    t[:size] = dev(torch, a)
+    t[stride:stride + size] = dev(torch, b)
+    r = gpu_ctx.measure_chunks_stream(t, size, 2, stride, *SMALL)
+    assert r == restate(S, [a, b], SMALL)
+    assert r.chunks // 2 < r.unique_chunks < r.chunks    # only the chunks around byte 2500 differ
+    del t
+    torch.cuda.empty_cache()
+
+
+def test_bytes_around_the_objects_are_not_read(S, torch, gpu_ctx):
+    """The result does not change with the bytes before the buffer, in the gap and
+    after the last object (whose end shares a 16-byte piece with them)."""
+    size, stride, n, lead = 4096 + 1001, 4096 + 1008, 3, 4096
+    objs = [random_bytes(size, 30 + j) for j in range(n)]
+    want = restate(S, objs, SMALL)
+    for poison in (0x00, 0xFF, 57):
+        host = np.full(lead + n * stride + 4096, poison, np.uint8)
+        for j, o in enumerate(objs):
+            host[lead + j * stride:lead + j * stride + size] = o
+        t = dev(torch, host)
+        assert gpu_ctx.measure_chunks_stream(t[lead:], size, n, stride, *SMALL) == want, poison
+        with gpu_ctx.chunker(100, 64, 1000) as h:        # bits = 6: byte 57 is a candidate wherever it is read
+            h.add_stream(t[lead:], size, n, stride)
+            assert h.result() == restate(S, objs, (100, 64, 1000)), poison
+
+
+# ---- 7. shift -----------------------------------------------------------------------------------
+
+def test_shifted_copy_deduplicates(S, torch, gpu_ctx):
+    """B = one extra byte + A: content-defined cuts find A's chunks again, which
+    fixed blocks cannot."""
+    a = random_bytes(MiB, 40)
+    b = np.concatenate([np.full(1, 0x5C, np.uint8), a])
+    want = restate(S, [a, b], DEFAULTS)
+    assert want.unique_bytes < 0.6 * (len(a) + len(b))
+    with gpu_ctx.chunker() as h:
+        h.add(dev(torch, a))
+        h.add(dev(torch, np.concatenate([b, np.full(15, 0, np.uint8)])), len(b))
+        got = h.result()
+    assert got == want
+    fixed = gpu_ctx.chunker(4096, 8192, 4096)
+    fixed.add(dev(torch, a))
+    fixed.add(dev(torch, np.concatenate([b, np.full(15, 0, np.uint8)])), len(b))
+    assert fixed.result().unique_bytes == len(a) + len(b)
+    fixed.close()
+
+
+# ---- 8. accumulation ------------------------------------------------------------------------------
+
+def test_adds_accumulate(S, torch, gpu_ctx):
+    size, n, stride = 30011, 4, 30016
+    objs = [random_bytes(size, 50 + j) for j in range(n)]
+    t = dev(torch, strided(objs, stride, 0))
+    with gpu_ctx.chunker(*SMALL) as h:
+        assert h.result() == S.ChunkResult()
+        h.add_stream(t, size, n, stride)
+        r1 = h.result()
+        assert r1 == h.result() == restate(S, objs, SMALL)      # result() changes nothing
+        h.add_stream(t, size, n, stride)                         # the same again: nothing new
+        r2 = h.result()
+        assert (r2.bytes, r2.chunks, r2.candidates, r2.forced_cuts) == \
+            (2 * r1.bytes, 2 * r1.chunks, 2 * r1.candidates, 2 * r1.forced_cuts)
+        assert (r2.unique_chunks, r2.unique_bytes) == (r1.unique_chunks, r1.unique_bytes)
+        h.reset()
+        assert h.result() == S.ChunkResult()
+        h.add(t, size)
+        assert h.result() == restate(S, objs[:1], SMALL)
+        h.add_stream(0, 0, 5)                  # zero-length adds launch nothing, whatever the pointer
+        h.add_stream(0, 4096, 0)
+        assert h.result() == restate(S, objs[:1], SMALL)
+
+
+def test_ring_overwritten_on_one_stream(S, torch, gpu_ctx):
+    """Four payloads pass through one buffer on one stream, no sync between."""
+    size = 200003
+    parts = [random_bytes(size, 60 + k) for k in range(3)] + [random_bytes(size, 60)]
+    srcs = [dev(torch, p) for p in parts]
+    ring = torch.zeros(size + 13, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    st = torch.cuda.Stream()
+    with gpu_ctx.chunker(*SMALL) as h:
+        with torch.cuda.stream(st):
+            for s in srcs:
+                ring[:size].copy_(s, non_blocking=True)
+                h.add(ring, size, stream=st)
+        r = h.result()
+    st.synchronize()
+    assert r == restate(S, parts, SMALL)
+    assert r.unique_bytes == 3 * size
+
+
+def test_two_streams_two_threads(S, torch, gpu_ctx):
+    parts = [random_bytes(300007, 70), random_bytes(MiB + 5, 1)]
+    ts = [dev(torch, np.concatenate([p, np.zeros(16, np.uint8)])) for p in parts]
+    torch.cuda.synchronize()               # the uploads ran on the default stream
+    errs = []
+    with gpu_ctx.chunker(*SMALL) as h:
+        def work(k):
+            try:
+                st = torch.cuda.Stream()
+                for _ in range(4):
+                    h.add(ts[k], len(parts[k]), stream=st)
+            except Exception as e:   # pragma: no cover
+                errs.append(e)
+        th = [threading.Thread(target=work, args=(k,)) for k in range(2)]
+        for x in th:
+            x.start()
+        for x in th:
+            x.join()
+        assert not errs
+        r = h.result()
+    want = restate(S, parts, SMALL)
+    assert (r.bytes, r.chunks, r.candidates, r.forced_cuts) == \
+        (4 * want.bytes, 4 * want.chunks, 4 * want.candidates, 4 * want.forced_cuts)
+    assert (r.unique_chunks, r.unique_bytes) == (want.unique_chunks, want.unique_bytes)
+
+
+def test_array_growth(S, torch, gpu_ctx):
+    """Many small chunks in adds of growing size: the handle's arrays double several times."""
+    sizes = [1000, 50001, 100003, 200001, 400007, 700001]
+    parts = [random_bytes(n, 80 + k) for k, n in enumerate(sizes)]
+    with gpu_ctx.chunker(*SMALL) as h:
+        for k, p in enumerate(parts):
+            h.add(dev(torch, np.concatenate([p, np.zeros(16, np.uint8)])), len(p))
+            if k == 2:
+                assert h.result() == restate(S, parts[:3], SMALL)
+        r = h.result()
+    assert r == restate(S, parts, SMALL)
+    assert sum(n // 32 + 2 for n in sizes) > 8 * 4096       # slots: at least three doublings from 4096
+
+
+# ---- 9. host form -----------------------------------------------------------------------------------
+
+def test_host_buffers(S):
+    a = random_bytes(MiB + 5)
+    want = restate(S, [a], SMALL)
+    pad = np.zeros(a.size + 64, np.uint8)
+    for off in (0, 1, 3, 17):                            # unaligned
+        pad[off:off + a.size] = a
+        assert S.measure_chunks_data(pad[off:off + a.size], *SMALL) == want, off
+    assert S.measure_chunks_data(bytes(a), *SMALL) == want                         # read-only
+    assert S.measure_chunks_data(memoryview(bytes(a)), *SMALL) == want
+    ro = np.array(a)
+    ro.setflags(write=False)
+    assert S.measure_chunks_data(ro) == restate(S, [a], DEFAULTS)
+    assert S.measure_chunks_data(b"", *SMALL) == S.ChunkResult()
+
+
+def test_host_buffer_across_the_copy_edge(S):
+    """More than one 64 MiB staging copy, a crafted window across the copy's edge."""
+    w = window13()
+    edge = 64 * MiB
+    size = edge + 5003
+    a = zeros_with(size, [edge - 40000, edge + 10, edge + 3000], w)
+    want = restate(S, [a], DEFAULTS)
+    assert want.candidates >= 3
+    assert S.measure_chunks_data(a) == want
+    b = np.empty(size + 1, np.uint8)
+    b[1:] = a
+    assert S.measure_chunks_data(b[1:]) == want          # unaligned: the edge falls elsewhere in the caller's memory
+
+
+# ---- 10. refusals ------------------------------------------------------------------------------------
+
+def test_refusals(S, torch, gpu_ctx):
+    t = torch.zeros(3 * 4096 + 32, dtype=torch.uint8, device="cuda:0")
+    for bad, msg in [((2048, 8000, 65536), "power of two"), ((2048, 32, 65536), "power of two"),
+                     ((2048, 1 << 25, 1 << 26), "power of two"), ((31, 64, 256), "at least 32"),
+                     ((300, 64, 256), "exceed max_bytes"), ((2048, 8192, (1 << 30) + 1), "2\\^30")]:
+        with pytest.raises(ValueError, match=msg):
+            gpu_ctx.chunker(*bad)
+    with gpu_ctx.chunker() as h:
+        with pytest.raises(ValueError, match="16-byte aligned"):
+            h.add_stream(t[8:], 4096, 2, 4096)
+        with pytest.raises(ValueError, match="16-byte aligned"):
+            h.add_stream(t, 4096, 2, 4104)
+        with pytest.raises(ValueError, match="overlap"):
+            h.add_stream(t, 8192, 2, 4096)
+        assert h.result() == S.ChunkResult()
+    assert gpu_ctx.measure_chunks(t[:4096 + 16], 4096 + 16, 1 << 30, 1 << 24, 1 << 30).chunks == 1
