@@ -465,6 +465,81 @@ int s3dg_chunks_pass_seconds(s3dg_chunks *h, double *seconds);
 int s3dg_chunk_data(const uint8_t *buf, uint64_t len, uint64_t min_bytes, uint64_t avg_bytes,
                     uint64_t max_bytes, s3dg_chunk_result *out);
 
+/* ---- LZ4 compressed size per store block (read-only) -------
+ * What a payload is worth to a store that compresses independent blocks of
+ * `block_bytes`: the bytes it takes after a greedy LZ4 block compressor, the
+ * answer to the generator's `compress` knob that zero bytes and byte entropy
+ * cannot give (a repeated base block has neither and shrinks twelvefold).  No
+ * seed is needed.  Only sizes are computed; the definition is exact, and
+ * `size` is the length of a valid LZ4 block for every input.
+ *
+ * block_bytes: a multiple of 4096 from 4096 to 65536, so every match offset
+ * fits LZ4's 16 bits.  Every object is cut into blocks from its first byte;
+ * the last block of an object has whatever length n >= 1 remains.  No match
+ * reaches outside its block.  For one block b[0..n):
+ *  1. For 0 <= i <= n - 4, v(i) is the little-endian u32 at i and
+ *     H(i) = (v(i) * 2654435761 mod 2^32) >> 20, 12 bits.
+ *  2. Candidates, in groups of 64 positions.  T is a table of 4096 entries,
+ *     all empty at first.  For every i <= n - 4, c(i) = T[H(i)] as it stood
+ *     before i's group: the greatest j < 64 * (i / 64) with H(j) = H(i), or
+ *     none.  After a group's lookups T[h] becomes the greatest i of the group
+ *     with H(i) = h.  Every position is entered, those inside a match too.
+ *  3. src(i), for i <= n - 12 only (LZ4's last match start): c(i) if it exists
+ *     and v(c(i)) = v(i); otherwise i - 1 if i >= 1 and v(i - 1) = v(i) (a run
+ *     of five equal bytes); otherwise none.  Blocks with n < 13 have no match.
+ *  4. Greedy parse from anchor = p = 0: take the smallest i >= p with a source
+ *     s; L is the largest length with b[s + k] = b[i + k] for k < L and
+ *     i + L <= n - 5 (the last five bytes are literals; the source may overlap
+ *     the match; L >= 4; no backward extension).  With lit = i - anchor,
+ *     size += 1 + ext(lit) + lit + 2 + ext(L - 4), where ext(x) = 0 for
+ *     x < 15 and 1 + (x - 15) / 255 otherwise; anchor = p = i + L; repeat.
+ *     When no source is left, lit = n - anchor and size += 1 + ext(lit) + lit.
+ *
+ * A handle accumulates over adds on any stream, like s3dg_measure, and holds
+ * eight device words; an add needs no scratch.  One wave compresses one block
+ * at a time with the block and the table in LDS (block_bytes + 8 KiB).
+ * Out of scope: emitting the compressed bytes; any compressor but this one
+ * (zstd's entropy stage would be a second feature); blocks above 64 KiB;
+ * matches across blocks or objects; a bench.py config (tools/lz_rate.py
+ * times the pass).
+ * Destroy a handle before its context. */
+typedef struct s3dg_lz s3dg_lz;
+typedef struct {
+    uint64_t bytes;          /* payload bytes measured (stride gaps excluded) */
+    uint64_t blocks;         /* blocks compressed, ragged last blocks included */
+    uint64_t lz_bytes;       /* sum of size */
+    uint64_t stored_bytes;   /* sum of min(size, n): a store keeps a block raw when compression does not pay */
+    uint64_t raw_blocks;     /* blocks with size >= n */
+    uint64_t matches;
+    uint64_t match_bytes;    /* sum of L */
+    uint64_t literal_bytes;  /* literal_bytes + match_bytes == bytes */
+} s3dg_lz_result;
+int s3dg_lz_create(s3dg_ctx *ctx, uint64_t block_bytes, s3dg_lz **out);
+int s3dg_lz_destroy(s3dg_lz *h);
+int s3dg_lz_reset(s3dg_lz *h);   /* waits for the enqueued adds; an empty handle again */
+/* n_objs objects of obj_size bytes at src + j*stride (device memory; the
+ * refusals of s3dg_measure_add_stream).  Asynchronous on `stream` and ordered
+ * like a fill: a later launch on the same stream may overwrite src.  Stride
+ * gaps and whatever follows the last object are never read.  The adds share
+ * only the handle's totals, which take atomics, so adds from several threads
+ * on several streams are safe.  A zero-length add launches nothing. */
+int s3dg_lz_add_stream(s3dg_lz *h, const void *src, uint64_t obj_size, uint64_t stride,
+                       uint64_t n_objs, void *stream);
+/* Blocks [blk_lo, blk_hi) of one obj_size-byte object, in units of
+ * block_bytes, block blk_lo at src (blk_hi is clipped to the object): one
+ * large object passing through a smaller buffer.  Blocks are independent, so
+ * ranges that add up to the object give the object's result exactly. */
+int s3dg_lz_add_range(s3dg_lz *h, const void *src, uint64_t obj_size, uint64_t blk_lo,
+                      uint64_t blk_hi, void *stream);
+/* Waits for the enqueued adds and fills *out.  The handle is unchanged: get
+ * again, or add and get.  An empty handle yields all zeros. */
+int s3dg_lz_get(s3dg_lz *h, s3dg_lz_result *out);
+/* A host buffer (any alignment, read-only memory included) as one object, on
+ * a host slot's GPU: copied in chunks of whole blocks (up to 64 MiB) on the
+ * slot's two streams in turn, each chunk an s3dg_lz_add_range.
+ * len == 0: all zeros, no GPU needed. */
+int s3dg_lz_data(const uint8_t *buf, uint64_t len, uint64_t block_bytes, s3dg_lz_result *out);
+
 /* ---- memory / copy helpers ------------------------------------------------ */
 int s3dg_device_alloc(s3dg_ctx *ctx, uint64_t bytes, void **out);
 int s3dg_device_free(s3dg_ctx *ctx, void *p);

@@ -65,6 +65,12 @@ class ChunkRec(ctypes.Structure):
                 ("candidates", c_u64), ("forced_cuts", c_u64)]
 
 
+class LzRec(ctypes.Structure):
+    """s3dg_lz_result"""
+    _fields_ = [("bytes", c_u64), ("blocks", c_u64), ("lz_bytes", c_u64), ("stored_bytes", c_u64),
+                ("raw_blocks", c_u64), ("matches", c_u64), ("match_bytes", c_u64), ("literal_bytes", c_u64)]
+
+
 # name -> (restype, argtypes); the exact export list of include/s3dlio_gpu.h
 SIGNATURES = {
     "s3dg_ctx_create": (c_int, [c_int, ctypes.POINTER(c_vp)]),
@@ -129,6 +135,13 @@ SIGNATURES = {
     "s3dg_chunks_set_option": (c_int, [c_vp, c_int, c_int]),
     "s3dg_chunks_pass_seconds": (c_int, [c_vp, ctypes.POINTER(ctypes.c_double)]),
     "s3dg_chunk_data": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, ctypes.POINTER(ChunkRec)]),
+    "s3dg_lz_create": (c_int, [c_vp, c_u64, ctypes.POINTER(c_vp)]),
+    "s3dg_lz_destroy": (c_int, [c_vp]),
+    "s3dg_lz_reset": (c_int, [c_vp]),
+    "s3dg_lz_add_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp]),
+    "s3dg_lz_add_range": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp]),
+    "s3dg_lz_get": (c_int, [c_vp, ctypes.POINTER(LzRec)]),
+    "s3dg_lz_data": (c_int, [c_vp, c_u64, c_u64, ctypes.POINTER(LzRec)]),
     "s3dg_write_ceiling": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
     "s3dg_write_ceiling_tiled": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
     "s3dg_write_ceiling_fill": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),

@@ -143,6 +143,43 @@ class ChunkResult:
                    int(r.forced_cuts))
 
 
+@dataclass(frozen=True)
+class LzResult:
+    """s3dg_lz_result: what a payload takes in a store that compresses
+    independent blocks with a greedy LZ4."""
+    bytes: int = 0            # payload bytes measured (stride gaps excluded)
+    blocks: int = 0           # blocks compressed, ragged last blocks included
+    lz_bytes: int = 0         # summed LZ4 block sizes
+    stored_bytes: int = 0     # summed min(size, n): a block that does not shrink is kept raw
+    raw_blocks: int = 0       # blocks with size >= n
+    matches: int = 0
+    match_bytes: int = 0
+    literal_bytes: int = 0    # literal_bytes + match_bytes == bytes
+
+    @property
+    def ratio(self) -> float:
+        """bytes / stored_bytes: what the store saves (n : 1)."""
+        return self.bytes / self.stored_bytes if self.stored_bytes else 0.0
+
+    @property
+    def lz_ratio(self) -> float:
+        """bytes / lz_bytes: the compressor's own ratio, below 1 for incompressible data."""
+        return self.bytes / self.lz_bytes if self.lz_bytes else 0.0
+
+    @property
+    def match_fraction(self) -> float:
+        return self.match_bytes / self.bytes if self.bytes else 0.0
+
+    @property
+    def raw_fraction(self) -> float:
+        return self.raw_blocks / self.blocks if self.blocks else 0.0
+
+    @classmethod
+    def _of(cls, r) -> "LzResult":
+        return cls(int(r.bytes), int(r.blocks), int(r.lz_bytes), int(r.stored_bytes), int(r.raw_blocks),
+                   int(r.matches), int(r.match_bytes), int(r.literal_bytes))
+
+
 CHUNK_DEFAULTS = (2048, 8192, 65536)   # min_bytes, avg_bytes, max_bytes
 _CHUNKS_TIME_PASSES, _CHUNKS_GEAR_TABLE = 1, 2   # S3DG_CHUNKS_* options
 
@@ -572,6 +609,28 @@ class Context:
             h.add_stream(src, obj_size, n_objs, stride, stream=stream)
             return h.result()
 
+    # -- LZ4 compressed size per store block (read-only) ---------------------------
+    # The bytes a payload takes in a store that compresses independent blocks
+    # of `block_bytes` (a multiple of 4096 up to 65536) with a greedy LZ4
+    # (DESIGN.md §5.12).  Blocks are cut from each object's start.
+    def lz_measurer(self, block_bytes: int = 65536) -> "LzMeasure":
+        """An accumulating handle: add / add_stream / add_range on any stream,
+        then result()."""
+        return LzMeasure(self, block_bytes)
+
+    def measure_lz(self, src, nbytes: int | None = None, block_bytes: int = 65536, stream=None) -> LzResult:
+        """One object of `nbytes` at src."""
+        with self.lz_measurer(block_bytes) as m:
+            m.add(src, nbytes, stream=stream)
+            return m.result()
+
+    def measure_lz_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None,
+                          block_bytes: int = 65536, stream=None) -> LzResult:
+        """n_objs equal objects as fill_stream lays them out; stride gaps are never read."""
+        with self.lz_measurer(block_bytes) as m:
+            m.add_stream(src, obj_size, n_objs, stride, stream=stream)
+            return m.result()
+
     def write_ceiling(self, dst, nbytes: int | None = None, pattern: int = 0xA5A5A5A5,
                       stream=None) -> None:
         n = _nbytes(dst) if nbytes is None else int(nbytes)
@@ -650,6 +709,65 @@ class Measure:
     def close(self) -> None:
         if getattr(self, "_h", None):
             call("s3dg_measure_destroy", self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LzMeasure:
+    """s3dg_lz: an LZ4 size measurement that accumulates over calls and streams
+    (Context.lz_measurer).  The adds are asynchronous on their stream and
+    ordered like a fill, so a following launch on the same stream may overwrite
+    the buffer; result() waits for them and leaves the handle unchanged."""
+
+    def __init__(self, ctx: Context, block_bytes: int = 65536):
+        self._ctx = ctx
+        self.block_bytes = int(block_bytes)
+        h = c_vp()
+        call("s3dg_lz_create", ctx._h, self.block_bytes, ctypes.byref(h))
+        self._h = h
+
+    def add(self, src, nbytes: int | None = None, stream=None) -> None:
+        """One object of `nbytes` at src."""
+        n = _nbytes(src) if nbytes is None else int(nbytes)
+        self.add_stream(src, n, 1, stride=0, stream=stream)   # one object: no stride to align
+
+    def add_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None, stream=None) -> None:
+        """n_objs objects of obj_size bytes, object j at src + j*stride."""
+        stride = obj_size if stride is None else stride
+        need = (int(n_objs) - 1) * int(stride) + int(obj_size) if n_objs > 0 and obj_size > 0 else 0
+        call("s3dg_lz_add_stream", self._h, self._ctx._src(src, need), int(obj_size), int(stride),
+             int(n_objs), self._ctx._s(stream))
+
+    def add_range(self, src, obj_size: int, blk_lo: int, blk_hi: int, stream=None) -> None:
+        """Blocks [blk_lo, blk_hi) (units of block_bytes) of one obj_size-byte
+        object, block blk_lo at src."""
+        hi = min(int(blk_hi) * self.block_bytes, int(obj_size))
+        need = max(0, hi - int(blk_lo) * self.block_bytes)
+        call("s3dg_lz_add_range", self._h, self._ctx._src(src, need), int(obj_size), int(blk_lo),
+             int(blk_hi), self._ctx._s(stream))
+
+    def result(self) -> LzResult:
+        r = _lib.LzRec()
+        call("s3dg_lz_get", self._h, ctypes.byref(r))
+        return LzResult._of(r)
+
+    def reset(self) -> None:
+        call("s3dg_lz_reset", self._h)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            call("s3dg_lz_destroy", self._h)
             self._h = None
 
     def __enter__(self):
