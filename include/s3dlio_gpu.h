@@ -289,6 +289,46 @@ int s3dg_verify_controlled_stream(s3dg_ctx *ctx, const void *src, uint64_t obj_s
                                   uint64_t n_objs, uint64_t dedup, uint32_t f_num, uint32_t f_den,
                                   uint64_t seed_base, uint64_t first_obj, void *stream,
                                   s3dg_verify_result *out);
+/* Read-side twin of s3dg_fill_controlled_batch: object k of `descs` (its
+ * dst_off read as the byte offset of the object from src_base) is recomputed
+ * from (size, dedup, f_num/f_den, entropy, base block) and compared with the
+ * bytes in memory.  Synchronous on `stream`.  Nothing is written to the payload;
+ * no byte at or past an object's end is read.
+ *
+ * *out (totals; required): mismatched_bytes and mismatched_blocks are summed
+ * over the objects, blocks being 4 KiB blocks counted within each object;
+ * first_offset is the lowest differing byte offset from src_base over all
+ * objects, whatever order the descriptors come in (UINT64_MAX = none).
+ *
+ * per_obj (host array of n, or NULL): per_obj[k] holds the same three fields
+ * for the caller's descriptor k, first_offset counted from that object's first
+ * byte.  An empty object (size == 0) is clean: {0, 0, UINT64_MAX}.
+ *
+ * Descriptors are independent of each other: they may come in any order, leave
+ * gaps and overlap.  Two descriptors over the same bytes are two checks, and a
+ * byte that is wrong for both counts twice in the totals.  Empty objects are
+ * allowed anywhere in the array.
+ *
+ * Refusals (S3DG_EINVAL, each with a message; nothing is enqueued after the
+ * refusal is found): a null `out` ("null output"); null `descs` with n > 0
+ * ("null descriptor array"); a null or not 16-byte aligned src_base; and the
+ * fill's rules for each non-empty descriptor with the fill's messages
+ * ("dst_off must be a multiple of 16", "need f_num < f_den", "object larger
+ * than 2^31 blocks"), the first offending descriptor naming the refusal.
+ * f_den == 0, the random-data layout, is refused here as the fill's batch
+ * refuses it.  Unlike the fill, the call validates all descriptors before the
+ * first launch: a refused call has read nothing, and `out` and `per_obj` are
+ * written only on success.
+ *
+ * n == 0, or all objects empty, launches nothing and is clean.  Calls on
+ * different streams of one context share no state; two threads on two streams
+ * are safe.  Waves per block follow s3dg_set_waves_per_block (auto: 2, as the
+ * other verify calls); tiles follow s3dg_set_batch_tile for 2..64 blocks
+ * (otherwise 8..64 blocks, chosen per sub-batch).  Results are identical. */
+int s3dg_verify_controlled_batch(s3dg_ctx *ctx, const void *src_base,
+                                 const s3dg_obj_desc *descs, uint64_t n, void *stream,
+                                 s3dg_verify_result *out,       /* totals; required */
+                                 s3dg_verify_result *per_obj);  /* host array of n, or NULL */
 /* The read-side twins of s3dg_xoshiro_fill / s3dg_dgen_fill /
  * s3dg_dgen_fill_stream (the keystream layouts: the npz x-fill and DG1), under
  * the same rules as the calls above: the GPU regenerates each chunk's keystream

@@ -115,6 +115,8 @@ SIGNATURES = {
     "s3dg_verify_random_data": (c_int, [c_vp, c_vp, c_u64, c_u64, c_vp, ctypes.POINTER(VerifyRec)]),
     "s3dg_verify_controlled_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_u64, c_u32, c_u32,
                                               c_u64, c_u64, c_vp, ctypes.POINTER(VerifyRec)]),
+    "s3dg_verify_controlled_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(ObjDesc), c_u64, c_vp,
+                                             ctypes.POINTER(VerifyRec), ctypes.POINTER(VerifyRec)]),
     "s3dg_verify_xoshiro": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp, ctypes.POINTER(VerifyRec)]),
     "s3dg_verify_dgen": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_u64, c_u32, c_u32, c_u64, c_vp,
                                  ctypes.POINTER(VerifyRec)]),

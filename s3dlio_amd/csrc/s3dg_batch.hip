@@ -21,7 +21,20 @@ struct TileCount {
     }
 };
 
+// tile records of one object of a verify launch (no lead; an empty object has none)
+struct VerifyTileCount {
+    uint32_t tshift;
+    __host__ __device__ uint64_t operator()(const s3dg_obj_desc &o) const { return verify_obj_tiles(o.size, tshift); }
+};
+
 }  // namespace
+
+hipError_t launch_verify_batch_scan(const s3dg_obj_desc *d, uint64_t n, uint32_t tshift, uint64_t *rec_lo, void *tmp,
+                                    size_t *tmp_bytes, hipStream_t s) {
+    hipcub::TransformInputIterator<uint64_t, VerifyTileCount, const s3dg_obj_desc *> it(d, VerifyTileCount{tshift});
+    if (n > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    return hipcub::DeviceScan::ExclusiveSum(tmp, *tmp_bytes, it, rec_lo, (int)n, s);
+}
 
 hipError_t launch_batch_scan(const s3dg_obj_desc *d, uint64_t n, uint32_t tshift, uintptr_t base, uint64_t *rec_lo,
                              void *tmp, size_t *tmp_bytes, hipStream_t s) {

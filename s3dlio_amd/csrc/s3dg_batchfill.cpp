@@ -92,6 +92,10 @@ private:
     uint64_t gen_ = 0;
 };
 
+}  // namespace
+
+namespace s3dg {
+
 // The stream's batch state, made on its first batch: the upload stream and
 // the events of both staging sets and both record maps.
 int batch_state_init(StreamState *S) {
@@ -128,6 +132,10 @@ int stage_reserve(StreamState::Stage &G, uint64_t n, hipStream_t up) {
     G.cap = cap;
     return S3DG_OK;
 }
+
+}  // namespace s3dg
+
+namespace {
 
 // One pass over d[k0, k1) in parts (validate, count, stage into H), merged in order.
 BatchScan scan_sub_batch(const s3dg_obj_desc *d, uint64_t k0, uint64_t k1, uintptr_t base, s3dg_obj_desc *H,

@@ -117,6 +117,7 @@ void stream_state_free(StreamState *S) {
     for (hipEvent_t e : {S->zfork, S->zjoin})
         if (e) (void)hipEventDestroy(e);
     if (S->ks.dev) (void)hipFree(S->ks.dev);
+    if (S->vobj) (void)hipFree(S->vobj);
     delete S;
 }
 

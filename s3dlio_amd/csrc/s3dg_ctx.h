@@ -1,7 +1,7 @@
 // s3dg_ctx.h — the context behind the C ABI: its fields, the per-stream launch
 // state and the measured defaults.  Private to the units that implement
 // include/s3dlio_gpu.h over the context (s3dg_capi.cpp, s3dg_tune.cpp,
-// s3dg_fill.cpp, s3dg_batchfill.cpp, s3dg_keystream.cpp); everything else
+// s3dg_fill.cpp, s3dg_batchfill.cpp, s3dg_verify_batch.cpp, s3dg_keystream.cpp); everything else
 // reaches a context through the functions of s3dg_internal.h.
 #pragma once
 #include "s3dg_internal.h"
@@ -183,6 +183,10 @@ struct StreamState {
         hipEvent_t consumed = nullptr;  // device copy may be freed (k_batch_map done; both on `up`)
     } stage[2];
     int next = 0;
+    // per-object result records of batch verify calls on this stream (device),
+    // grown on demand; a call is synchronous, so the next one finds them idle
+    VerifyRec *vobj = nullptr;
+    uint64_t vobj_cap = 0;
     // queue counters of persistent keystream launches on this stream
     KsCounters ks;
     // lifetime (under the context's mu): users holding the state, and whether
@@ -328,6 +332,14 @@ int verify_with_record(s3dg_ctx *c, hipStream_t s, const char *launch_what,
 // A record map of at least `tiles` records in place of *map (s3dg_fill.cpp).
 // The caller has waited for every launch that reads the old one.
 int tile_map_grow(TileRec **map, uint64_t *cap, uint64_t tiles);
+
+// The stream's batch state (s3dg_batchfill.cpp), shared by the batch fill and
+// the batch verify: the upload stream and the events of both staging sets and
+// both record maps, made on the stream's first batch call; and staging set G
+// with room for n descriptors (its host buffer is free once its last upload
+// finished, its device side once the map kernel that read it finished).
+int batch_state_init(StreamState *S);
+int stage_reserve(StreamState::Stage &G, uint64_t n, hipStream_t up);
 
 // n_objs objects of obj_size bytes at dst + j*stride, entropy seed_base +
 // ((first_obj + j) << 32), prefix parameters pp.  Large streams whose objects

@@ -8,6 +8,7 @@
 
 #include "s3dlio_gpu.h"
 #include "s3dg_batch_plan.h"   // kBlk, the batch tile-shift range
+#include "s3dg_verify_batch_plan.h"
 
 // Sets the calling thread's error text (s3dg_last_error) and returns code.
 extern "C" int s3dg_internal_fail(int code, const char *msg);
@@ -93,6 +94,33 @@ hipError_t launch_verify_stream(const LaunchCfg &lc, const uint8_t *src, uint64_
                                 uint64_t first_obj, PrefixParams pp, const void *base_dev, uint64_t off0,
                                 VerifyRec *rec, hipStream_t s);
 hipError_t verify_rec_reset(VerifyRec *rec, hipStream_t s);   // {0, 0, UINT64_MAX}, on the stream
+
+// Batch verify (k_verify_batch): one tile (2^tshift slots)
+// of an object, TileRec's layout with the object's index in its sub-batch
+// where the fill keeps its XCD lead (a verify launch has none: slot k of the
+// tile is block first + k).
+struct VTileRec {
+    uint64_t src_off;      // byte offset of the object
+    uint64_t size;         // object size
+    uint64_t entropy;
+    uint32_t first;        // first block of the tile
+    uint32_t obj;          // descriptor index within the sub-batch
+    PrefixParams pp;
+};
+static_assert(sizeof(VTileRec) == sizeof(TileRec), "VTileRec is one s_load_dwordx16, in TileRec's maps");
+// rec_lo[k] = sum of verify_obj_tiles(d[j].size, tshift) for j < k (empty objects: none).
+// tmp == nullptr: *tmp_bytes = the scratch size n needs.
+hipError_t launch_verify_batch_scan(const s3dg_obj_desc *d, uint64_t n, uint32_t tshift, uint64_t *rec_lo, void *tmp,
+                                    size_t *tmp_bytes, hipStream_t s);
+// Records of a sub-batch's n uploaded descriptors (empty ones included, in the caller's order).
+hipError_t launch_verify_batch_map(const s3dg_obj_desc *d, uint64_t n, const uint64_t *rec_lo, VTileRec *tiles,
+                                   uint32_t tshift, hipStream_t s);
+// The compare over recs << tshift slots, in sub-launches of at most
+// kVerifyMaxGrid: adds to *tot (offsets from src_base) and, when pobj is not
+// null, to pobj[record's obj] (offsets from the object's first byte).
+hipError_t launch_verify_batch(int waves_per_block, const uint8_t *src_base, const VTileRec *tiles, uint64_t recs,
+                               uint32_t tshift, const void *base_dev, VerifyRec *tot, VerifyRec *pobj, hipStream_t s);
+hipError_t launch_verify_recs_reset(VerifyRec *recs, uint64_t n, hipStream_t s);   // n x {0, 0, UINT64_MAX}
 
 // Batch records built on the device from the uploaded descriptors (the scan,
 // then k_batch_map: prefix parameters per object and its records), then

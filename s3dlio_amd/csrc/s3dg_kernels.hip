@@ -557,6 +557,111 @@ __global__ __launch_bounds__(64 * NW) void k_fill_batch(uint8_t *dst_base, const
     }
 }
 
+// Batch verify, the read-side twin of k_fill_batch as k_verify_stream is of
+// k_fill_stream: workgroup g -> tile record g >> tshift
+// (one scalar load), block first + (g mod 2^tshift) of that object; a slot
+// past the object's end exits, uniformly for the workgroup.  No lead: nothing
+// is stored, so slots need not follow the XCD dealing.  Phases 1-2 are the
+// fill's; phase 3 is k_verify_stream's compare: whole 16-byte pieces (those
+// that end at or below the block's length) loaded nontemporally before the
+// plan, the ragged piece of an object's last block read byte by byte below
+// its length, zeros expected below c and the image above.  Thread 0 of a
+// block with differences makes three vector atomics on the call's totals
+// (offsets from src_base) and three on its object's record (offsets from the
+// object's start; pobj null: totals only); a clean block touches no memory.
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void k_verify_batch(const uint8_t *src_base, const VTileRec *tiles, uint64_t g0,
+                                                          uint32_t tshift, const u32x4 *base, VerifyRec *tot,
+                                                          VerifyRec *pobj) {
+    constexpr int T = 64 * NW, SPL = 4 / NW;
+    __shared__ __attribute__((aligned(16))) BlockLds S;
+    __shared__ uint32_t wcnt[NW], wfirst[NW];
+    const uint32_t t = threadIdx.x;
+    const uint32_t lane = t & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const uint64_t g = g0 + blockIdx.x;
+    const uint64_t tile = g >> tshift;
+    // the record in ONE scalar load issued first, then the base block's
+    // vector loads, as k_fill_batch; the wait "redefines" raw, so no use of
+    // the record moves above it
+    u32x16 raw;
+    asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(raw) : "s"(tiles + tile) : "memory");
+    u32x4 B[SPL], G[SPL];
+    load_base<NW>(B, t, base);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(raw) :: "memory");
+    const VTileRec e = __builtin_bit_cast(VTileRec, raw);
+    const uint32_t i = e.first + (uint32_t)(g & ((1u << tshift) - 1));
+    const uint64_t boff = (uint64_t)i * kBlk;
+    if (boff >= e.size) return;                                   // uniform for the whole workgroup
+    const uint8_t *bs = src_base + e.src_off + boff;
+    const uint64_t left = e.size - boff;
+    const uint32_t L = left < kBlk ? (uint32_t)left : kBlk;       // = Plan::L
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+        const uint32_t o = (t + k * T) * 16;
+        G[k] = u32x4{0u, 0u, 0u, 0u};
+        if (o + 16 <= L) G[k] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(bs + o));
+    }
+    Plan P;
+    if (wave == 0) {
+        plan_block<false>(P, lane, i, e.size, e.entropy, e.pp);
+        if (lane == 0) { S.meta[0] = P.c; S.meta[1] = P.L; }
+    }
+    store_image<NW>(S, t, B);
+    __syncthreads();
+    if (wave == 0) patch_image(S, P, lane);
+    __syncthreads();
+    const uint32_t c = S.meta[0];
+    uint32_t cnt = 0, first = kBlk;                               // kBlk: no differing byte
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+        const uint32_t o = (t + k * T) * 16;
+        if (o >= L) continue;
+        u32x4 x = {0u, 0u, 0u, 0u};
+        if (o + 16 > c) x = *reinterpret_cast<const u32x4 *>(S.img + o);
+        if (o + 16 <= L) {
+            x ^= G[k];
+            if (x.x | x.y | x.z | x.w) diff_piece(x, o, cnt, first);
+        } else {                                                  // ragged object tail: bytes < L only
+            const uint32_t dw[4] = {x.x, x.y, x.z, x.w};
+            for (uint32_t b = 0; o + b < L; ++b)
+                if (bs[o + b] != (uint8_t)(dw[b >> 2] >> (8 * (b & 3)))) {
+                    ++cnt;
+                    first = o + b < first ? o + b : first;
+                }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        cnt += __shfl_xor(cnt, d, 64);
+        const uint32_t f = __shfl_xor(first, d, 64);
+        first = f < first ? f : first;
+    }
+    if constexpr (NW > 1) {
+        if (lane == 0) { wcnt[wave] = cnt; wfirst[wave] = first; }
+        __syncthreads();
+        if (t == 0) {
+#pragma unroll
+            for (int w = 1; w < NW; ++w) {
+                cnt += wcnt[w];
+                first = wfirst[w] < first ? wfirst[w] : first;
+            }
+        }
+    }
+    if (t == 0 && cnt) {
+        typedef unsigned long long ull;
+        atomicAdd(reinterpret_cast<ull *>(&tot->bytes), (ull)cnt);
+        atomicAdd(reinterpret_cast<ull *>(&tot->blocks), 1ull);
+        atomicMin(reinterpret_cast<ull *>(&tot->first), (ull)(e.src_off + boff + first));
+        if (pobj) {
+            VerifyRec *r = pobj + e.obj;
+            atomicAdd(reinterpret_cast<ull *>(&r->bytes), (ull)cnt);
+            atomicAdd(reinterpret_cast<ull *>(&r->blocks), 1ull);
+            atomicMin(reinterpret_cast<ull *>(&r->first), (ull)(boff + first));
+        }
+    }
+}
+
 // Prefix parameters of one object on the device, as the host's make_prefix
 // (src/data_gen.rs:162-175; s3dg_unique_blocks' f64 round half away from zero).
 __device__ PrefixParams dev_make_prefix(uint64_t nb, uint64_t dedup, uint32_t f_num, uint32_t f_den) {
@@ -638,6 +743,58 @@ __global__ __launch_bounds__(256) void k_batch_map(const s3dg_obj_desc *d, uint6
             tiles[q] = b;
         }
     }
+}
+
+// Records of a verify sub-batch from its uploaded descriptors, one thread per
+// descriptor k (empty ones included, so k is the record's object index):
+// records [scan[k], scan[k] + verify_obj_tiles) of object k, record q's first
+// block (q - scan[k]) << tshift.  Objects with many records are written by the
+// whole wave, as in k_batch_map.
+__global__ __launch_bounds__(256) void k_verify_batch_map(const s3dg_obj_desc *d, uint64_t n, const uint64_t *scan,
+                                                          VTileRec *tiles, uint32_t tshift) {
+    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63;
+    VTileRec r{};
+    uint64_t rec_lo = 0, rec_hi = 0;
+    if (k < n) {
+        const s3dg_obj_desc o = d[k];
+        if (o.size) {   // an empty object has no records, and its other fields are not looked at
+            rec_lo = scan[k];
+            rec_hi = rec_lo + verify_obj_tiles(o.size, tshift);
+            r.src_off = o.dst_off;
+            r.size = o.size;
+            r.entropy = o.entropy;
+            r.obj = (uint32_t)k;
+            r.pp = dev_make_prefix((o.size + kBlk - 1) / kBlk, o.dedup, o.f_num, o.f_den);
+        }
+    }
+    const bool own = rec_hi - rec_lo <= kMapOwnRecords;
+    if (own)
+        for (uint64_t q = rec_lo; q < rec_hi; ++q) {
+            r.first = (uint32_t)((q - rec_lo) << tshift);
+            tiles[q] = r;
+        }
+    uint64_t big = __ballot(!own);
+    while (big) {
+        const int src = __builtin_ctzll(big);
+        big &= big - 1;
+        VTileRec b;
+        uint32_t *bw = reinterpret_cast<uint32_t *>(&b);
+        const uint32_t *rw = reinterpret_cast<const uint32_t *>(&r);
+#pragma unroll
+        for (int w = 0; w < 16; ++w) bw[w] = __builtin_amdgcn_readlane(rw[w], src);
+        const uint64_t lo = readlane64(rec_lo, src), hi = readlane64(rec_hi, src);
+        for (uint64_t q = lo + lane; q < hi; q += 64) {
+            b.first = (uint32_t)((q - lo) << tshift);
+            tiles[q] = b;
+        }
+    }
+}
+
+// n result records set to "clean": {0, 0, UINT64_MAX}.
+__global__ __launch_bounds__(256) void k_verify_recs_reset(VerifyRec *recs, uint64_t n) {
+    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < n) recs[k] = VerifyRec{0, 0, UINT64_MAX};
 }
 
 // tiles[q] for a uniform stream: n objects of obj_size bytes at dst_off =
@@ -1465,6 +1622,49 @@ hipError_t launch_batch_map(const s3dg_obj_desc *d, uint64_t n, const uint64_t *
     hipLaunchKernelGGL(k_batch_map, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, d, n, rec_lo, tiles, tshift,
                        (uint64_t)base, lead0, first_off);
     return hipGetLastError();
+}
+
+hipError_t launch_verify_batch_map(const s3dg_obj_desc *d, uint64_t n, const uint64_t *rec_lo, VTileRec *tiles,
+                                   uint32_t tshift, hipStream_t s) {
+    (void)hipGetLastError();
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_verify_batch_map, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, d, n, rec_lo, tiles,
+                       tshift);
+    return hipGetLastError();
+}
+
+hipError_t launch_verify_recs_reset(VerifyRec *recs, uint64_t n, hipStream_t s) {
+    (void)hipGetLastError();
+    constexpr uint64_t per = kMaxGridX * 256;
+    for (uint64_t k0 = 0; k0 < n; k0 += per) {
+        const uint64_t m = n - k0 < per ? n - k0 : per;
+        hipLaunchKernelGGL(k_verify_recs_reset, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, s, recs + k0, m);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// No occupancy cap, as launch_verify_stream: the pass only reads.  Every
+// sub-launch starts on a tile: kVerifyMaxGrid is a multiple of every tile size.
+hipError_t launch_verify_batch(int waves_per_block, const uint8_t *src_base, const VTileRec *tiles, uint64_t recs,
+                               uint32_t tshift, const void *base_dev, VerifyRec *tot, VerifyRec *pobj, hipStream_t s) {
+    static_assert(kVerifyMaxGrid == kMaxGridX, "the launchers' grid limit");
+    (void)hipGetLastError();
+    const u32x4 *b = reinterpret_cast<const u32x4 *>(base_dev);
+    const uint64_t total = recs << tshift;
+    for (uint64_t g0 = 0; g0 < total; g0 += kVerifyMaxGrid) {
+        const dim3 g((uint32_t)((total - g0) < kVerifyMaxGrid ? (total - g0) : kVerifyMaxGrid));
+        if (waves_per_block == 1)
+            hipLaunchKernelGGL((k_verify_batch<1>), g, dim3(64), 0, s, src_base, tiles, g0, tshift, b, tot, pobj);
+        else if (waves_per_block == 4)
+            hipLaunchKernelGGL((k_verify_batch<4>), g, dim3(256), 0, s, src_base, tiles, g0, tshift, b, tot, pobj);
+        else
+            hipLaunchKernelGGL((k_verify_batch<2>), g, dim3(128), 0, s, src_base, tiles, g0, tshift, b, tot, pobj);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_fill_uniform_tiles(const LaunchCfg &lc, uint8_t *dst, uint64_t obj_size, uint64_t stride,

@@ -73,6 +73,26 @@ class VerifyResult:
 
 
 @dataclass(frozen=True)
+class BatchVerifyResult:
+    """What Context.verify_batch found: the totals over the batch and, unless
+    it was called with per_object=False, every object that is not clean."""
+    total: VerifyResult = VerifyResult()   # counts summed over the objects; first_offset from the buffer's start
+    objects: int = 0                       # descriptors checked, empty ones included
+    # (index, VerifyResult) of every object that is not clean, in index order,
+    # first_offset from the object's first byte; None with per_object=False
+    mismatches: tuple | None = ()
+
+    @property
+    def ok(self) -> bool:
+        return self.total.ok
+
+    @property
+    def mismatched_objects(self) -> int | None:
+        """Objects that are not clean; None when the call asked for totals only."""
+        return None if self.mismatches is None else len(self.mismatches)
+
+
+@dataclass(frozen=True)
 class MeasureResult:
     """s3dg_measure_result: what a payload looks like to a store that
     deduplicates and compresses at the measured block size."""
@@ -489,6 +509,35 @@ class Context:
             if size:
                 need = max(need, int(off) + int(size))
         call("s3dg_fill_controlled_batch", self._h, self._dst(dst, need), arr, len(objs), self._s(stream))
+
+    def verify_batch(self, src, objects, stream=None, per_object: bool = True) -> BatchVerifyResult:
+        """The read-side twin of fill_batch: objects is fill_batch's iterable of
+        (off, size, entropy, dedup, compress), checked against `src`'s size
+        before any launch (ValueError).  The library validates every
+        descriptor before its first launch, so a call that raises has read
+        nothing.  Descriptors may come in any order, leave gaps and overlap.
+        per_object=False asks for the totals only (mismatches is None)."""
+        objs = list(objects)
+        arr = (ObjDesc * max(1, len(objs)))()
+        need = 0
+        for k, (off, size, ent, dd, comp) in enumerate(objs):
+            fn, fd = compress_ratio(comp)
+            arr[k] = ObjDesc(int(off), int(size), int(ent) & (2**64 - 1), int(dd), fn, fd)
+            if size:
+                need = max(need, int(off) + int(size))
+        tot = _lib.VerifyRec()
+        per = (_lib.VerifyRec * max(1, len(objs)))() if per_object else None
+        call("s3dg_verify_controlled_batch", self._h, self._src(src, need), arr, len(objs), self._s(stream),
+             ctypes.byref(tot), per)
+        mism = None
+        if per_object:
+            mism = ()
+            if tot.mismatched_bytes:
+                # the records as one array: only the dirty ones become Python objects
+                a = np.frombuffer(per, dtype=np.uint64, count=3 * len(objs)).reshape(-1, 3)
+                mism = tuple((int(k), VerifyResult(int(a[k, 0]), int(a[k, 1]), int(a[k, 2])))
+                             for k in np.flatnonzero(a[:, 0]))
+        return BatchVerifyResult(VerifyResult._of(tot), len(objs), mism)
 
     def xoshiro_fill(self, dst, nbytes: int | None = None, chunk_bytes: int = 2 << 20,
                      seed_base: int = 0, stream=None) -> None:
