@@ -30,8 +30,6 @@ inline const char *chunk_params_check(uint64_t min_bytes, uint64_t avg_bytes, ui
     return nullptr;
 }
 
-inline uint64_t chunk_align256(uint64_t n) { return (n + 255) / 256 * 256; }
-
 // One add: n_objs objects of `len` bytes each, object j at src + j*stride,
 // each chunked on its own.  Pass A writes one candidate bit per byte (a
 // 64-bit word per 64 bytes, 64 words per 4 KiB granule) and the number of
@@ -61,12 +59,11 @@ inline const char *chunk_plan_stream(ChunkPlan *P, uint64_t src, uint64_t obj_si
     *P = ChunkPlan{};
     if (min_bytes < kChunkWindow || min_bytes > kChunkMaxMax) return "min_bytes out of range";
     if (obj_size == 0 || n_objs == 0) return nullptr;
-    if (!src || (src & 15u) || (stride & 15u)) return "src and stride must be 16-byte aligned";
-    if (n_objs > 1 && stride < obj_size) return "stride < obj_size: objects overlap";
-    const uint64_t gpo = obj_size / kMeasureGranule + (obj_size % kMeasureGranule != 0);
+    if (const char *w = span_check(src, obj_size, stride, n_objs)) return w;
+    const uint64_t gpo = span_ceil_div(obj_size, kMeasureGranule);
     if (gpo > 0xFFFFFFFFull) return "object range larger than 2^32 granules";
     if (n_objs > kMeasureMaxSlots / gpo) return "more than 2^40 granules in one add";
-    const uint64_t rpo = obj_size / min_bytes + (obj_size % min_bytes != 0) + 1;
+    const uint64_t rpo = span_ceil_div(obj_size, min_bytes) + 1;
     if (n_objs > kChunkMaxSlots / rpo) return "more than 2^31 - 1 chunk slots in one add";
     P->n_objs = n_objs;
     P->len = obj_size;
@@ -76,38 +73,34 @@ inline const char *chunk_plan_stream(ChunkPlan *P, uint64_t src, uint64_t obj_si
     P->slots = n_objs * rpo;
     P->bytes = n_objs * obj_size;
     P->granules = n_objs * gpo;
-    P->nx = (gpo + kMeasureMaxGridX - 1) / kMeasureMaxGridX;
-    P->ny = (n_objs + kMeasureMaxGridY - 1) / kMeasureMaxGridY;
+    P->nx = span_nx(gpo);
+    P->ny = span_ny(n_objs);
     P->off_offset = P->granules * 512;                               // a multiple of 256
-    P->len_offset = P->off_offset + chunk_align256(P->slots * 8);
-    P->cnt_offset = P->len_offset + chunk_align256(P->slots * 4);
-    P->gcnt_offset = P->cnt_offset + chunk_align256(n_objs * 4);
-    P->scratch_bytes = P->gcnt_offset + chunk_align256(P->granules * 4);
+    P->len_offset = P->off_offset + span_align256(P->slots * 8);
+    P->cnt_offset = P->len_offset + span_align256(P->slots * 4);
+    P->gcnt_offset = P->cnt_offset + span_align256(n_objs * 4);
+    P->scratch_bytes = P->gcnt_offset + span_align256(P->granules * 4);
     return nullptr;
 }
 
 // Sub-launch (ix, iy) of pass A: objects [y0, y0 + gy), granules [x0, x0 + gx).
 inline void chunk_sub_launch(const ChunkPlan &P, uint64_t ix, uint64_t iy, uint64_t *x0, uint32_t *gx, uint64_t *y0,
                              uint32_t *gy) {
-    *x0 = ix * kMeasureMaxGridX;
-    *y0 = iy * kMeasureMaxGridY;
-    const uint64_t rx = P.gpo - *x0, ry = P.n_objs - *y0;
-    *gx = (uint32_t)(rx < kMeasureMaxGridX ? rx : kMeasureMaxGridX);
-    *gy = (uint32_t)(ry < kMeasureMaxGridY ? ry : kMeasureMaxGridY);
+    span_sub_launch(P.gpo, P.n_objs, ix, iy, x0, gx, y0, gy);
 }
 
 // The handle's arrays (a 16-byte fingerprint and a 4-byte length per slot)
-// grow by doubling from kMeasureMinCap slots, never beyond kChunkMaxSlots.
+// grow by doubling from kSpanMinCap slots, never beyond kChunkMaxSlots.
 inline uint64_t chunk_grow_cap(uint64_t cap, uint64_t need) {
-    uint64_t c = measure_grow_cap(cap, need);
+    uint64_t c = span_grow_cap(cap, need);
     return c > kChunkMaxSlots && need <= kChunkMaxSlots ? kChunkMaxSlots : c;
 }
 
 // Distinct count of n slots: two arrays of n 64-bit keys and two of n 32-bit
 // slot indices (in and out of the radix sort), each rounded up to 256 bytes;
 // hipCUB's own scratch comes on top (asked from hipCUB at run time).
-inline uint64_t chunk_sort_key_bytes(uint64_t n) { return chunk_align256(n * 8); }
-inline uint64_t chunk_sort_idx_bytes(uint64_t n) { return chunk_align256(n * 4); }
+inline uint64_t chunk_sort_key_bytes(uint64_t n) { return span_align256(n * 8); }
+inline uint64_t chunk_sort_idx_bytes(uint64_t n) { return span_align256(n * 4); }
 inline uint64_t chunk_sort_bytes(uint64_t n) { return 2 * chunk_sort_key_bytes(n) + 2 * chunk_sort_idx_bytes(n); }
 
 }  // namespace s3dg

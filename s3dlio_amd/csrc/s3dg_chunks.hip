@@ -326,11 +326,6 @@ __global__ __launch_bounds__(256) void k_chunk_count(const MeasureFp *fp, const 
     }
 }
 
-uint32_t grid_for(uint64_t n) {   // grid-stride kernels: up to 2048 workgroups of 256
-    const uint64_t g = (n + 255) / 256;
-    return (uint32_t)(g < 2048 ? (g ? g : 1) : 2048);
-}
-
 }  // namespace
 
 hipError_t launch_chunk_candidates(const ChunkPlan &P, const uint8_t *src, uint64_t stride, uint32_t shift, bool table,
@@ -357,7 +352,7 @@ hipError_t launch_chunk_candidates(const ChunkPlan &P, const uint8_t *src, uint6
             if (e != hipSuccess) return e;
         }
     }
-    hipLaunchKernelGGL(k_chunk_sum, dim3(grid_for(P.granules)), dim3(256), 0, s, gcnt, P.granules,
+    hipLaunchKernelGGL(k_chunk_sum, dim3(span_grid_for(P.granules)), dim3(256), 0, s, gcnt, P.granules,
                        &tot[kChunkTotCandidates]);
     return hipGetLastError();
 }
@@ -404,18 +399,18 @@ hipError_t launch_chunk_distinct(const MeasureFp *fp, const uint32_t *flen, uint
     idx_b = reinterpret_cast<uint32_t *>(w + 2 * kb + ib);
     void *tmp = w + 2 * kb + 2 * ib;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_chunk_keys_lo, dim3(grid_for(n)), dim3(256), 0, s, fp, flen, n, key_a, idx_a);
+    hipLaunchKernelGGL(k_chunk_keys_lo, dim3(span_grid_for(n)), dim3(256), 0, s, fp, flen, n, key_a, idx_a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     // stable LSD passes: by the low half, then by the high half
     e = hipcub::DeviceRadixSort::SortPairs(tmp, *tmp_bytes, key_a, key_b, idx_a, idx_b, (int)n, 0, 64, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_chunk_keys_hi, dim3(grid_for(n)), dim3(256), 0, s, fp, flen, n, idx_b, key_a);
+    hipLaunchKernelGGL(k_chunk_keys_hi, dim3(span_grid_for(n)), dim3(256), 0, s, fp, flen, n, idx_b, key_a);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = hipcub::DeviceRadixSort::SortPairs(tmp, *tmp_bytes, key_a, key_b, idx_b, idx_a, (int)n, 0, 64, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_chunk_count, dim3(grid_for(n)), dim3(256), 0, s, fp, flen, n, idx_a, tot);
+    hipLaunchKernelGGL(k_chunk_count, dim3(span_grid_for(n)), dim3(256), 0, s, fp, flen, n, idx_a, tot);
     return hipGetLastError();
 }
 

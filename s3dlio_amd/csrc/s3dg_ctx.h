@@ -1,7 +1,9 @@
 // s3dg_ctx.h — the context behind the C ABI: its fields, the per-stream launch
 // state and the measured defaults.  Private to the units that implement
 // include/s3dlio_gpu.h over the context (s3dg_capi.cpp, s3dg_tune.cpp,
-// s3dg_fill.cpp, s3dg_batchfill.cpp, s3dg_verify_batch.cpp, s3dg_keystream.cpp); everything else
+// s3dg_fill.cpp, s3dg_batchfill.cpp, s3dg_verify_batch.cpp, s3dg_keystream.cpp,
+// and, through s3dg_accum.h, s3dg_measure.cpp, s3dg_chunks.cpp and
+// s3dg_lz.cpp); everything else
 // reaches a context through the functions of s3dg_internal.h.
 #pragma once
 #include "s3dg_internal.h"

@@ -35,6 +35,7 @@
 // hold it: s3dlio_amd.register_host_buffer, HostRegistration in the Rust
 // patch).
 #include "s3dg_internal.h"
+#include "s3dg_span_plan.h"
 #include "s3dlio_gpu.h"
 
 #include <sys/random.h>
@@ -55,7 +56,7 @@ using namespace s3dg;
 
 namespace {
 
-constexpr uint64_t kChunk = 64ull << 20;       // bytes per device staging chunk
+constexpr uint64_t kChunk = kStagingChunk;     // bytes per device staging chunk
 constexpr uint64_t kSplitMin = 128ull << 20;   // smallest per-slot share of a split call
 constexpr int kMaxSlots = 64;
 // Calls that skip the copy engine (DESIGN.md §5.8 has the measurements):

@@ -5,6 +5,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "s3dg_span_plan.h"
+
 namespace s3dg {
 
 constexpr uint64_t kLzGranule = 4096;             // block_bytes is a multiple of this
@@ -14,7 +16,7 @@ constexpr uint64_t kLzCuLds = 160 * 1024;         // LDS of one gfx950 CU
 constexpr uint64_t kLzMaxWavesPerCu = 32;
 constexpr uint64_t kLzMaxBlocks = 1ull << 40;     // blocks of one add
 constexpr uint64_t kLzMaxGrid = 0x7FFFFFFFull;
-constexpr uint64_t kLzHostChunk = 64ull << 20;    // a host slot's staging chunk
+constexpr uint64_t kLzHostChunk = kStagingChunk;  // a host slot's staging chunk
 constexpr int kLzTotWords = 8;                    // s3dg_lz_result's fields, in order
 
 // block_bytes: a multiple of 4096 from 4096 to 65536.
@@ -38,7 +40,7 @@ struct LzPlan {
 inline const char *lz_plan_fill(LzPlan *P, uint64_t len, uint64_t n_objs, uint64_t block_bytes) {
     P->n_objs = n_objs;
     P->len = len;
-    P->bpo = len / block_bytes + (len % block_bytes != 0);
+    P->bpo = span_ceil_div(len, block_bytes);
     if (n_objs > kLzMaxBlocks / P->bpo) return "more than 2^40 blocks in one add";
     P->last_block = len - (P->bpo - 1) * block_bytes;
     P->blocks = n_objs * P->bpo;
@@ -53,8 +55,7 @@ inline const char *lz_plan_stream(LzPlan *P, uint64_t src, uint64_t obj_size, ui
     *P = LzPlan{};
     if (const char *w = lz_block_bytes_check(block_bytes)) return w;
     if (obj_size == 0 || n_objs == 0) return nullptr;
-    if (!src || (src & 15u) || (stride & 15u)) return "src and stride must be 16-byte aligned";
-    if (n_objs > 1 && stride < obj_size) return "stride < obj_size: objects overlap";
+    if (const char *w = span_check(src, obj_size, stride, n_objs)) return w;
     if (obj_size > (1ull << 56)) return "object larger than 2^56 bytes";
     return lz_plan_fill(P, obj_size, n_objs, block_bytes);
 }
@@ -65,13 +66,9 @@ inline const char *lz_plan_range(LzPlan *P, uint64_t src, uint64_t obj_size, uin
                                  uint64_t block_bytes) {
     *P = LzPlan{};
     if (const char *w = lz_block_bytes_check(block_bytes)) return w;
-    const uint64_t nb = obj_size / block_bytes + (obj_size % block_bytes != 0);
-    if (blk_hi > nb) blk_hi = nb;
-    if (blk_lo >= blk_hi) return nullptr;
-    if (!src || (src & 15u)) return "src must be a 16-byte aligned device pointer";
-    const uint64_t lo = blk_lo * block_bytes;                      // < obj_size
-    const uint64_t hi = blk_hi == nb ? obj_size : blk_hi * block_bytes;
-    return lz_plan_fill(P, hi - lo, 1, block_bytes);
+    uint64_t skip, len;
+    if (const char *w = span_clip(src, obj_size, blk_lo, blk_hi, block_bytes, &skip, &len)) return w;
+    return len ? lz_plan_fill(P, len, 1, block_bytes) : nullptr;
 }
 
 // One wave (a workgroup of its own) per block at a time: the block staged in

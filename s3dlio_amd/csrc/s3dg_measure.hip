@@ -280,11 +280,6 @@ __global__ __launch_bounds__(256) void k_hist_reduce(const uint32_t *part, uint3
 constexpr uint64_t kHistMaxGranules = 1ull << 19;
 uint32_t hist_grid_max(int cus) { return (uint32_t)(cus > 0 ? cus : 256) * 8; }
 
-uint32_t grid_for(uint64_t n) {   // grid-stride kernels: up to 2048 workgroups of 256
-    const uint64_t g = (n + 255) / 256;
-    return (uint32_t)(g < 2048 ? (g ? g : 1) : 2048);
-}
-
 }  // namespace
 
 hipError_t launch_measure_granules(const MeasurePlan &P, const uint8_t *src, uint64_t stride, int waves, void *rec,
@@ -366,7 +361,7 @@ hipError_t launch_measure_distinct(const MeasureFp *fp, uint64_t n, void *work, 
         return hipcub::DeviceRadixSort::SortPairs(nullptr, *tmp_bytes, lo_a, lo_b, hi_a, hi_b, (int)n, 0, 64, s);
     }
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_fp_split, dim3(grid_for(n)), dim3(256), 0, s, fp, n, lo_a, hi_a);
+    hipLaunchKernelGGL(k_fp_split, dim3(span_grid_for(n)), dim3(256), 0, s, fp, n, lo_a, hi_a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     // stable LSD passes: by the low half, then by the high half
@@ -374,7 +369,7 @@ hipError_t launch_measure_distinct(const MeasureFp *fp, uint64_t n, void *work, 
     if (e != hipSuccess) return e;
     e = hipcub::DeviceRadixSort::SortPairs(tmp, *tmp_bytes, hi_b, hi_a, lo_b, lo_a, (int)n, 0, 64, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_count_distinct, dim3(grid_for(n)), dim3(256), 0, s, lo_a, hi_a, n, distinct);
+    hipLaunchKernelGGL(k_count_distinct, dim3(span_grid_for(n)), dim3(256), 0, s, lo_a, hi_a, n, distinct);
     return hipGetLastError();
 }
 

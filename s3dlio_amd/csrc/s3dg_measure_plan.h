@@ -5,13 +5,15 @@
 #pragma once
 #include <stdint.h>
 
+#include "s3dg_span_plan.h"
+
 namespace s3dg {
 
 constexpr uint64_t kMeasureGranule = 4096;          // pass 1's unit: one workgroup
 constexpr uint64_t kMeasureMaxBlock = 1ull << 30;   // largest block_bytes
-constexpr uint64_t kMeasureMaxGridX = 1ull << 22;   // granules of one object per sub-launch
-constexpr uint64_t kMeasureMaxGridY = 65535;        // objects per sub-launch
 constexpr uint64_t kMeasureMaxSlots = 1ull << 40;   // fingerprints one handle may hold
+// the shared limits under the names this plan's callers and sweep know them by
+constexpr uint64_t kMeasureMaxGridX = kSpanMaxGridX, kMeasureMaxGridY = kSpanMaxGridY, kMeasureMinCap = kSpanMinCap;
 
 // block_bytes: a positive multiple of 4096, at most 2^30.
 inline const char *measure_block_bytes_check(uint64_t block_bytes) {
@@ -41,8 +43,8 @@ inline const char *measure_plan_fill(MeasurePlan *P, uint64_t len, uint64_t n_ob
     P->n_objs = n_objs;
     P->len = len;
     P->gpb = (uint32_t)(block_bytes / kMeasureGranule);
-    P->gpo = len / kMeasureGranule + (len % kMeasureGranule != 0);
-    P->bpo = len / block_bytes + (len % block_bytes != 0);
+    P->gpo = span_ceil_div(len, kMeasureGranule);
+    P->bpo = span_ceil_div(len, block_bytes);
     if (P->gpo > 0xFFFFFFFFull) return "object range larger than 2^32 granules";
     if (n_objs > kMeasureMaxSlots / P->gpo) return "more than 2^40 granules in one add";
     P->last_block = len - (P->bpo - 1) * block_bytes;
@@ -50,8 +52,8 @@ inline const char *measure_plan_fill(MeasurePlan *P, uint64_t len, uint64_t n_ob
     P->slots = n_objs * P->bpo;
     P->records = n_objs * P->gpo;
     P->bytes = n_objs * len;   // <= 2^40 * 4096
-    P->nx = (P->gpo + kMeasureMaxGridX - 1) / kMeasureMaxGridX;
-    P->ny = (n_objs + kMeasureMaxGridY - 1) / kMeasureMaxGridY;
+    P->nx = span_nx(P->gpo);
+    P->ny = span_ny(n_objs);
     return nullptr;
 }
 
@@ -63,8 +65,7 @@ inline const char *measure_plan_stream(MeasurePlan *P, uint64_t src, uint64_t ob
     *P = MeasurePlan{};
     if (const char *w = measure_block_bytes_check(block_bytes)) return w;
     if (obj_size == 0 || n_objs == 0) return nullptr;
-    if (!src || (src & 15u) || (stride & 15u)) return "src and stride must be 16-byte aligned";
-    if (n_objs > 1 && stride < obj_size) return "stride < obj_size: objects overlap";
+    if (const char *w = span_check(src, obj_size, stride, n_objs)) return w;
     return measure_plan_fill(P, obj_size, n_objs, block_bytes);
 }
 
@@ -74,25 +75,17 @@ inline const char *measure_plan_range(MeasurePlan *P, uint64_t src, uint64_t obj
                                       uint64_t blk_hi, uint64_t block_bytes) {
     *P = MeasurePlan{};
     if (const char *w = measure_block_bytes_check(block_bytes)) return w;
-    const uint64_t nb = obj_size / block_bytes + (obj_size % block_bytes != 0);
-    if (blk_hi > nb) blk_hi = nb;
-    if (blk_lo >= blk_hi) return nullptr;
-    if (!src || (src & 15u)) return "src must be a 16-byte aligned device pointer";
-    const uint64_t lo = blk_lo * block_bytes;                      // < obj_size
-    const uint64_t hi = blk_hi == nb ? obj_size : blk_hi * block_bytes;
-    P->skip = lo;
-    const char *w = measure_plan_fill(P, hi - lo, 1, block_bytes);
-    return w;
+    uint64_t skip, len;
+    if (const char *w = span_clip(src, obj_size, blk_lo, blk_hi, block_bytes, &skip, &len)) return w;
+    if (len == 0) return nullptr;
+    P->skip = skip;
+    return measure_plan_fill(P, len, 1, block_bytes);
 }
 
 // Sub-launch (ix, iy) of a plan: objects [y0, y0 + gy), granules [x0, x0 + gx).
 inline void measure_sub_launch(const MeasurePlan &P, uint64_t ix, uint64_t iy, uint64_t *x0, uint32_t *gx,
                                uint64_t *y0, uint32_t *gy) {
-    *x0 = ix * kMeasureMaxGridX;
-    *y0 = iy * kMeasureMaxGridY;
-    const uint64_t rx = P.gpo - *x0, ry = P.n_objs - *y0;
-    *gx = (uint32_t)(rx < kMeasureMaxGridX ? rx : kMeasureMaxGridX);
-    *gy = (uint32_t)(ry < kMeasureMaxGridY ? ry : kMeasureMaxGridY);
+    span_sub_launch(P.gpo, P.n_objs, ix, iy, x0, gx, y0, gy);
 }
 
 // Bytes of pass 1's per-granule records: a 16-byte partial fingerprint and a
@@ -103,15 +96,10 @@ inline uint64_t measure_record_zero_offset(uint64_t records) { return records * 
 // Distinct count of n fingerprints: four arrays of n 64-bit words (the low and
 // high halves, in and out of the radix sort), each rounded up to 256 bytes;
 // hipCUB's own scratch comes on top (asked from hipCUB at run time).
-inline uint64_t measure_sort_array_bytes(uint64_t n) { return (n * 8 + 255) / 256 * 256; }
+inline uint64_t measure_sort_array_bytes(uint64_t n) { return span_align256(n * 8); }
 inline uint64_t measure_sort_bytes(uint64_t n) { return 4 * measure_sort_array_bytes(n); }
 
 // The fingerprint array grows by doubling from kMeasureMinCap slots.
-constexpr uint64_t kMeasureMinCap = 4096;
-inline uint64_t measure_grow_cap(uint64_t cap, uint64_t need) {
-    uint64_t c = cap < kMeasureMinCap ? kMeasureMinCap : cap;
-    while (c < need) c *= 2;
-    return c;
-}
+inline uint64_t measure_grow_cap(uint64_t cap, uint64_t need) { return span_grow_cap(cap, need); }
 
 }  // namespace s3dg

@@ -713,158 +713,108 @@ class Context:
         return n.value
 
 
-class Measure:
+class _Accum:
+    """What Measure, LzMeasure and Chunker share: a C handle s3dg_<_sym>_* that
+    accumulates over calls and streams.  A subclass names the symbol prefix
+    (_sym), the result record of _lib (_rec), turns one into its result
+    (_result) and creates the handle with _open(*create_args)."""
+    _sym = _rec = None
+
+    def _open(self, ctx: Context, *args) -> None:
+        self._ctx = ctx
+        h = c_vp()
+        call(f"s3dg_{self._sym}_create", ctx._h, *args, ctypes.byref(h))
+        self._h = h
+
+    def add(self, src, nbytes: int | None = None, stream=None) -> None:
+        """One object of `nbytes` at src."""
+        n = _nbytes(src) if nbytes is None else int(nbytes)
+        self.add_stream(src, n, 1, stride=0, stream=stream)   # one object: no stride to align
+
+    def add_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None, stream=None) -> None:
+        """n_objs objects of obj_size bytes, object j at src + j*stride."""
+        stride = obj_size if stride is None else stride
+        need = (int(n_objs) - 1) * int(stride) + int(obj_size) if n_objs > 0 and obj_size > 0 else 0
+        call(f"s3dg_{self._sym}_add_stream", self._h, self._ctx._src(src, need), int(obj_size), int(stride),
+             int(n_objs), self._ctx._s(stream))
+
+    def result(self):
+        r = self._rec()
+        call(f"s3dg_{self._sym}_get", self._h, ctypes.byref(r))
+        return self._result(r)
+
+    def reset(self) -> None:
+        call(f"s3dg_{self._sym}_reset", self._h)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            call(f"s3dg_{self._sym}_destroy", self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _BlockAccum(_Accum):
+    """An _Accum over blocks of self.block_bytes: ranges of whole blocks too."""
+
+    def add_range(self, src, obj_size: int, blk_lo: int, blk_hi: int, stream=None) -> None:
+        """Blocks [blk_lo, blk_hi) (units of block_bytes) of one obj_size-byte
+        object, block blk_lo at src."""
+        hi = min(int(blk_hi) * self.block_bytes, int(obj_size))
+        need = max(0, hi - int(blk_lo) * self.block_bytes)
+        call(f"s3dg_{self._sym}_add_range", self._h, self._ctx._src(src, need), int(obj_size), int(blk_lo),
+             int(blk_hi), self._ctx._s(stream))
+
+
+class Measure(_BlockAccum):
     """s3dg_measure: a measurement that accumulates over calls and streams
     (Context.measurer).  The adds are asynchronous on their stream and ordered
     like a fill, so a following launch on the same stream may overwrite the
     buffer; result() waits for them and leaves the handle unchanged."""
+    _sym, _rec = "measure", _lib.MeasureRec
 
     def __init__(self, ctx: Context, block_bytes: int = 4096, hist: bool = False):
-        self._ctx = ctx
         self.block_bytes = int(block_bytes)
         self.hist = bool(hist)
-        h = c_vp()
-        call("s3dg_measure_create", ctx._h, self.block_bytes, 1 if hist else 0, ctypes.byref(h))
-        self._h = h
+        self._open(ctx, self.block_bytes, 1 if hist else 0)
 
-    def add(self, src, nbytes: int | None = None, stream=None) -> None:
-        """One object of `nbytes` at src."""
-        n = _nbytes(src) if nbytes is None else int(nbytes)
-        self.add_stream(src, n, 1, stride=0, stream=stream)   # one object: no stride to align
-
-    def add_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None, stream=None) -> None:
-        """n_objs objects of obj_size bytes, object j at src + j*stride."""
-        stride = obj_size if stride is None else stride
-        need = (int(n_objs) - 1) * int(stride) + int(obj_size) if n_objs > 0 and obj_size > 0 else 0
-        call("s3dg_measure_add_stream", self._h, self._ctx._src(src, need), int(obj_size), int(stride),
-             int(n_objs), self._ctx._s(stream))
-
-    def add_range(self, src, obj_size: int, blk_lo: int, blk_hi: int, stream=None) -> None:
-        """Blocks [blk_lo, blk_hi) (units of block_bytes) of one obj_size-byte
-        object, block blk_lo at src."""
-        hi = min(int(blk_hi) * self.block_bytes, int(obj_size))
-        need = max(0, hi - int(blk_lo) * self.block_bytes)
-        call("s3dg_measure_add_range", self._h, self._ctx._src(src, need), int(obj_size), int(blk_lo),
-             int(blk_hi), self._ctx._s(stream))
-
-    def result(self) -> MeasureResult:
-        r = _lib.MeasureRec()
-        call("s3dg_measure_get", self._h, ctypes.byref(r))
+    def _result(self, r) -> MeasureResult:
         return MeasureResult._of(r, self.hist)
 
-    def reset(self) -> None:
-        call("s3dg_measure_reset", self._h)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            call("s3dg_measure_destroy", self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class LzMeasure:
+class LzMeasure(_BlockAccum):
     """s3dg_lz: an LZ4 size measurement that accumulates over calls and streams
     (Context.lz_measurer).  The adds are asynchronous on their stream and
     ordered like a fill, so a following launch on the same stream may overwrite
     the buffer; result() waits for them and leaves the handle unchanged."""
+    _sym, _rec, _result = "lz", _lib.LzRec, staticmethod(LzResult._of)
 
     def __init__(self, ctx: Context, block_bytes: int = 65536):
-        self._ctx = ctx
         self.block_bytes = int(block_bytes)
-        h = c_vp()
-        call("s3dg_lz_create", ctx._h, self.block_bytes, ctypes.byref(h))
-        self._h = h
-
-    def add(self, src, nbytes: int | None = None, stream=None) -> None:
-        """One object of `nbytes` at src."""
-        n = _nbytes(src) if nbytes is None else int(nbytes)
-        self.add_stream(src, n, 1, stride=0, stream=stream)   # one object: no stride to align
-
-    def add_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None, stream=None) -> None:
-        """n_objs objects of obj_size bytes, object j at src + j*stride."""
-        stride = obj_size if stride is None else stride
-        need = (int(n_objs) - 1) * int(stride) + int(obj_size) if n_objs > 0 and obj_size > 0 else 0
-        call("s3dg_lz_add_stream", self._h, self._ctx._src(src, need), int(obj_size), int(stride),
-             int(n_objs), self._ctx._s(stream))
-
-    def add_range(self, src, obj_size: int, blk_lo: int, blk_hi: int, stream=None) -> None:
-        """Blocks [blk_lo, blk_hi) (units of block_bytes) of one obj_size-byte
-        object, block blk_lo at src."""
-        hi = min(int(blk_hi) * self.block_bytes, int(obj_size))
-        need = max(0, hi - int(blk_lo) * self.block_bytes)
-        call("s3dg_lz_add_range", self._h, self._ctx._src(src, need), int(obj_size), int(blk_lo),
-             int(blk_hi), self._ctx._s(stream))
-
-    def result(self) -> LzResult:
-        r = _lib.LzRec()
-        call("s3dg_lz_get", self._h, ctypes.byref(r))
-        return LzResult._of(r)
-
-    def reset(self) -> None:
-        call("s3dg_lz_reset", self._h)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            call("s3dg_lz_destroy", self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(ctx, self.block_bytes)
 
 
-class Chunker:
+class Chunker(_Accum):
     """s3dg_chunks: a content-defined chunking analysis that accumulates over
     calls and streams (Context.chunker).  The adds are asynchronous on their
     stream and ordered like a fill; every add holds whole objects.  result()
     waits for them and leaves the handle unchanged."""
+    _sym, _rec, _result = "chunks", _lib.ChunkRec, staticmethod(ChunkResult._of)
 
     def __init__(self, ctx: Context, min_bytes: int = CHUNK_DEFAULTS[0], avg_bytes: int = CHUNK_DEFAULTS[1],
                  max_bytes: int = CHUNK_DEFAULTS[2]):
-        self._ctx = ctx
         self.min_bytes, self.avg_bytes, self.max_bytes = int(min_bytes), int(avg_bytes), int(max_bytes)
-        h = c_vp()
-        call("s3dg_chunks_create", ctx._h, self.min_bytes, self.avg_bytes, self.max_bytes, ctypes.byref(h))
-        self._h = h
-
-    def add(self, src, nbytes: int | None = None, stream=None) -> None:
-        """One object of `nbytes` at src."""
-        n = _nbytes(src) if nbytes is None else int(nbytes)
-        self.add_stream(src, n, 1, stride=0, stream=stream)   # one object: no stride to align
-
-    def add_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None, stream=None) -> None:
-        """n_objs objects of obj_size bytes, object j at src + j*stride."""
-        stride = obj_size if stride is None else stride
-        need = (int(n_objs) - 1) * int(stride) + int(obj_size) if n_objs > 0 and obj_size > 0 else 0
-        call("s3dg_chunks_add_stream", self._h, self._ctx._src(src, need), int(obj_size), int(stride),
-             int(n_objs), self._ctx._s(stream))
-
-    def result(self) -> ChunkResult:
-        r = _lib.ChunkRec()
-        call("s3dg_chunks_get", self._h, ctypes.byref(r))
-        return ChunkResult._of(r)
-
-    def reset(self) -> None:
-        call("s3dg_chunks_reset", self._h)
+        self._open(ctx, self.min_bytes, self.avg_bytes, self.max_bytes)
 
     def time_passes(self, on: bool = True) -> None:
         """HIP events around the three passes of every following add (pass_seconds)."""
@@ -879,23 +829,6 @@ class Chunker:
         t = (ctypes.c_double * 3)()
         call("s3dg_chunks_pass_seconds", self._h, t)
         return float(t[0]), float(t[1]), float(t[2])
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            call("s3dg_chunks_destroy", self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def xoshiro_jump(state, n: int) -> list[int]:

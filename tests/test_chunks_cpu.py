@@ -1,9 +1,9 @@
 """CPU: the content-defined chunking surface without a GPU:
 the C calls' argument checks with their messages (a C program), the Python
 call's buffer handling, ChunkResult's derived values, and the chunk plan
-(csrc/s3dg_chunk_plan.h, compiled with g++ alone, plain and as a stand-alone
-program under the address and undefined-behaviour sanitizers) over a sweep of
-its inputs."""
+(csrc/s3dg_chunk_plan.h over csrc/s3dg_span_plan.h, compiled with g++ alone,
+plain and as a stand-alone program under the address and undefined-behaviour
+sanitizers) over a sweep of its inputs."""
 import dataclasses
 import os
 import shutil

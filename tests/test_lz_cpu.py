@@ -3,9 +3,9 @@ restatement of the definition (tests/lz_restatement.py) yields valid LZ4 blocks
 of exactly the stated size, the cross-check numbers of the definition, the
 reference's compress contract through the restatement, the C calls' argument
 checks (a C program), the Python call's buffer handling, LzResult's derived
-values, and the plan (csrc/s3dg_lz_plan.h, compiled with g++ alone, plain and
-under the address and undefined-behaviour sanitizers) over a sweep of its
-inputs."""
+values, and the plan (csrc/s3dg_lz_plan.h over csrc/s3dg_span_plan.h, compiled
+with g++ alone, plain and under the address and undefined-behaviour
+sanitizers) over a sweep of its inputs."""
 import dataclasses
 import os
 import shutil

@@ -1,8 +1,8 @@
 """CPU: the measurement surface without a GPU: the C calls' argument checks (a
 C program), the Python call's buffer handling, MeasureResult's derived values,
-and the measure plan (csrc/s3dg_measure_plan.h, compiled with g++ alone, plain
-and under the address and undefined-behaviour sanitizers) over a sweep of its
-inputs."""
+and the measure plan (csrc/s3dg_measure_plan.h over csrc/s3dg_span_plan.h,
+compiled with g++ alone, plain and under the address and undefined-behaviour
+sanitizers) over a sweep of its inputs."""
 import math
 import os
 import shutil
