@@ -3,7 +3,8 @@ the C calls' argument checks with their messages (a C program), the Python
 call's buffer handling, ChunkResult's derived values, and the chunk plan
 (csrc/s3dg_chunk_plan.h over csrc/s3dg_span_plan.h, compiled with g++ alone,
 plain and as a stand-alone program under the address and undefined-behaviour
-sanitizers) over a sweep of its inputs."""
+sanitizers) over a sweep of its inputs; and that the crafted objects of the GPU
+suite's fingerprint tests parse as meant under its restatement."""
 import dataclasses
 import os
 import shutil
@@ -156,6 +157,38 @@ def test_measure_result_keeps_its_fields():
                                                                     "hist"]
     assert [f[0] for f in MeasureRec._fields_] == ["bytes", "zero_bytes", "blocks", "unique_blocks", "hist"]
     assert [f[0] for f in ChunkRec._fields_] == [f.name for f in dataclasses.fields(S.ChunkResult)]
+
+
+# ---- the crafted inputs of the fingerprint tests ------------------------------------
+
+def test_crafted_chunk_cases_parse_as_meant():
+    """The objects that tests/test_gpu_chunks.py builds for pass C (its sections 8 to 11),
+    judged by that file's restatement alone: every base object has exactly the candidate
+    at its string's end, and per length at least 98 % of the flipped or exchanged
+    variants still are the first chunk [0, 31 + s] and two forced cuts (a flip may make a
+    candidate of its own; the GPU comparison stays exact then, the case only must not
+    drift from what it is for).  A condition on the inputs, not a measurement."""
+    import test_gpu_chunks as T
+    for M in T.SHORT + T.LONG:
+        for s in T.SHIFTS:
+            assert T.only_w_candidate(T.shifted_base(s, M), s), (s, M)
+            assert T.parsed_as_meant(T.shifted_base(s, M)[None], s, M) == 1, (s, M)
+        for s, o in enumerate(T.everywhere_case(M)):
+            assert T.only_w_candidate(o, s) and T.parsed_as_meant(o[None], s, M, 3) == 1, (s, M)
+    for t in (1, 3, 11):
+        for o in T.length_case(t):
+            assert T.only_w_candidate(o, 0), t
+    for name, case, lengths in (("every byte, short", T.every_byte_case, T.SHORT),
+                                ("every byte, long", T.every_byte_case, T.LONG),
+                                ("piece swaps", T.swap_case, T.LONG)):
+        meant = total = 0
+        for M in lengths:
+            rows = [case(s, M)[:-1] for s in T.SHIFTS]        # the base once, and its variants
+            m = sum(T.parsed_as_meant(r, s, M) for s, r in enumerate(rows))
+            n = sum(len(r) for r in rows)
+            assert m >= 0.98 * n, (name, M, m, n)
+            meant, total = meant + m, total + n
+        print(f"{name}: {meant} of {total} objects parse as meant")
 
 
 # ---- the plan --------------------------------------------------------------------

@@ -411,7 +411,240 @@ def test_shifted_copy_deduplicates(S, torch, gpu_ctx):
     fixed.close()
 
 
-# ---- 8. accumulation ------------------------------------------------------------------------------
+# ---- 8. pass C: a chunk at any shift, every byte of it in the fingerprint ---------------------------
+# Parameters (32, 65536, M).  An object is s filler bytes, the string of window16()
+# (the object's only candidate, so the first chunk is [0, 31 + s]) and K times M
+# bytes that forced cuts close: chunk k starts at byte 32 + s + k M, at shift
+# (s + k M) mod 16, and the last one ends with the object, unaligned for most s.
+# The builders below need no GPU; tests/test_chunks_cpu.py checks through the
+# restatement that the objects parse as meant.
+
+FP_AVG = 65536
+SHORT = tuple(range(48, 64))           # 3 or 4 pieces, every tail length 0..15
+LONG = (2064, 2065, 2072, 2079)        # 129 or 130 pieces (three laps of a lane), tails 0, 1, 8, 15
+SHIFTS = range(16)
+
+
+@functools.lru_cache(maxsize=None)
+def window16():
+    """A 32-byte string whose window hash passes at bits = 16 (found by search on the CPU)."""
+    rng = np.random.default_rng(16)
+    while True:
+        rows = rng.integers(1, 256, (1 << 16, 32), dtype=np.uint8)
+        hit = np.flatnonzero((window_hash(rows)[:, 0] >> np.uint32(16)) == 0)
+        if hit.size:
+            w = rows[hit[0]].copy()
+            w.setflags(write=False)
+            return w
+
+
+def only_w_candidate(obj, s):
+    """The object's one candidate at bits = 16 is the end of the string placed behind s bytes."""
+    return np.flatnonzero(candidates(obj, 16)[0]).tolist() == [31 + s]
+
+
+def parsed_as_meant(rows, s, M, K=2):
+    """How many of the equal-length objects are the chunks [0, 31 + s] and K forced cuts of M bytes."""
+    meant = [(0, 31 + s)] + [(32 + s + k * M, 31 + s + (k + 1) * M) for k in range(K)]
+    return sum(cuts_of(c, 32, M)[:2] == (meant, K) for c in candidates(rows, 16))
+
+
+@functools.lru_cache(maxsize=None)
+def shifted_base(s, M):
+    """filler(s) | w | X0 | X1, X0 and X1 of M bytes: the first seed whose object has no
+    candidate but w's end and whose X0 has no two equal chunk-relative 16-byte pieces
+    (so that no exchange of two is a no-op)."""
+    w = window16()
+    attempt = 0
+    while True:
+        rng = np.random.default_rng([8, s, M, attempt])
+        a = np.concatenate([rng.integers(0, 256, s, dtype=np.uint8), w, rng.integers(0, 256, 2 * M, dtype=np.uint8)])
+        pieces = a[32 + s:32 + s + M // 16 * 16].reshape(-1, 16)
+        if only_w_candidate(a, s) and len({bytes(p) for p in pieces}) == len(pieces):
+            a.setflags(write=False)
+            return a
+        attempt += 1
+
+
+def flip_set(M):
+    """The bytes of a chunk that get a variant: all of a short one; pieces 0, 1, 63, 64, 65
+    and the last two of a long one."""
+    if M < 1024:
+        return np.arange(M)
+    P = (M + 15) // 16
+    return np.array([q for p in (0, 1, 63, 64, 65, P - 2, P - 1) for q in range(16 * p, min(16 * p + 16, M))])
+
+
+@functools.lru_cache(maxsize=None)
+def every_byte_case(s, M):
+    """The base, one copy per byte q of flip_set(M) with bit (q + s) % 8 of that byte of X0
+    flipped, the same for X1, and the base again: one object per row."""
+    a = shifted_base(s, M)
+    qs = flip_set(M)
+    out = np.tile(a, (2 * qs.size + 2, 1))
+    bit = (1 << ((qs + s) % 8)).astype(np.uint8)
+    for k in (0, 1):
+        out[1 + k * qs.size + np.arange(qs.size), 32 + s + k * M + qs] ^= bit
+    out.setflags(write=False)
+    return out
+
+
+def swap_pairs(M):
+    """(p, q = p | 1 << b) over the whole pieces of a chunk of M bytes."""
+    P = M // 16
+    return [(p, p | (1 << b)) for p in range(P) for b in range(P.bit_length()) if not p >> b & 1 and p | (1 << b) < P]
+
+
+@functools.lru_cache(maxsize=None)
+def swap_case(s, M):
+    """The base, one copy per pair of swap_pairs(M) with the chunk-relative pieces p and q
+    of X0 exchanged (for s != 0 not 16-byte aligned in the object), and the base again."""
+    a = shifted_base(s, M)
+    o = 32 + s
+    pairs = swap_pairs(M)
+    out = np.tile(a, (len(pairs) + 2, 1))
+    for i, (p, q) in enumerate(pairs, 1):
+        out[i, o + 16 * p:o + 16 * p + 16] = a[o + 16 * q:o + 16 * q + 16]
+        out[i, o + 16 * q:o + 16 * q + 16] = a[o + 16 * p:o + 16 * p + 16]
+    out.setflags(write=False)
+    return out
+
+
+def strided_each(rows, stride):
+    """strided() with a poison of its own (never zero) behind every object."""
+    buf = np.empty((rows.shape[0], stride), np.uint8)
+    buf[:] = (1 + 37 * np.arange(rows.shape[0]) % 255).astype(np.uint8)[:, None]
+    buf[:, :rows.shape[1]] = rows
+    return buf.reshape(-1)
+
+
+def stream_of(torch, ctx, rows, params):
+    n, size = rows.shape
+    stride = (size + 15) // 16 * 16 + 16
+    return ctx.measure_chunks_stream(dev(torch, strided_each(rows, stride)), size, n, stride, *params)
+
+
+@pytest.mark.parametrize("M", SHORT + LONG)
+def test_fp_every_byte(S, torch, gpu_ctx, M):
+    """Every byte enters, at every shift and tail: a flipped bit anywhere in a chunk,
+    mid-object or at the object's unaligned end, is a chunk of its own."""
+    params = (32, FP_AVG, M)
+    for s in SHIFTS:
+        rows = every_byte_case(s, M)
+        n = rows.shape[0]
+        want = restate(S, list(rows), params)
+        assert want.bytes == rows.size and want.chunks >= 3 * n and 3 + (n - 2) <= want.unique_chunks
+        got = stream_of(torch, gpu_ctx, rows, params)
+        assert got == want, (s, M)
+
+
+# ---- 9. pass C: pieces are keyed by their index in the chunk ----------------------------------------
+
+@pytest.mark.parametrize("M", LONG)
+def test_fp_piece_swaps(S, torch, gpu_ctx, M):
+    """Two pieces of a chunk whose indices differ in one bit, exchanged: a chunk of its own."""
+    params = (32, FP_AVG, M)
+    for s in SHIFTS:
+        rows = swap_case(s, M)
+        n = rows.shape[0]
+        assert n - 2 == len(swap_pairs(M)) > 7 * 64
+        assert len({bytes(r) for r in rows}) == n - 1     # numpy: every variant differs from the base and the others
+        want = restate(S, list(rows), params)
+        assert want.unique_chunks >= 3 + (n - 2)
+        got = stream_of(torch, gpu_ctx, rows, params)
+        assert got == want, (s, M)
+
+
+# ---- 10. pass C: equal content is one fingerprint wherever it lies ----------------------------------
+
+@functools.lru_cache(maxsize=None)
+def everywhere_case(M):
+    """For every s the object filler(s) | w | X | Y_s | X, one X for all: it lies mid-object
+    and at the object's end, at every shift.  No candidate but w's end, the Y_s distinct."""
+    w = window16()
+    attempt = 0
+    while True:
+        rng = np.random.default_rng([10, M, attempt])
+        X = rng.integers(0, 256, M, dtype=np.uint8)
+        objs = [np.concatenate([rng.integers(0, 256, s, dtype=np.uint8), w, X, rng.integers(0, 256, M, dtype=np.uint8), X])
+                for s in SHIFTS]
+        mids = {bytes(o[32 + s + M:32 + s + 2 * M]) for s, o in enumerate(objs)} | {bytes(X)}
+        if all(only_w_candidate(o, s) for s, o in enumerate(objs)) and len(mids) == 17:
+            for o in objs:
+                o.setflags(write=False)
+            return tuple(objs)
+        attempt += 1
+
+
+@pytest.mark.parametrize("M", SHORT + LONG)
+def test_fp_same_chunk_everywhere(S, torch, gpu_ctx, M):
+    """A fingerprint that depended on the shift, on a byte past the chunk or on a byte past
+    the object would count more than one X."""
+    params = (32, FP_AVG, M)
+    objs = everywhere_case(M)
+    want = restate(S, objs, params)
+    assert want == S.ChunkResult(sum(len(o) for o in objs), 64, 33, sum(32 + s for s in SHIFTS) + 17 * M, 16, 48)
+    with gpu_ctx.chunker(*params) as h:
+        for s, o in enumerate(objs):                       # sizes differ: an add each, its own poison behind it
+            tail = np.full(16 + -len(o) % 16, 0x11 + 13 * s, np.uint8)
+            h.add(dev(torch, np.concatenate([o, tail])), len(o))
+        got = h.result()
+    assert got == want
+
+
+# ---- 11. pass C: length alone separates ---------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def length_case(t):
+    """w | Z with Z of 60 bytes, the last t zero (closed by a forced cut at max = 60), and
+    w | Z[:60 - t] (closed by the object's end): the same zero-padded pieces, the same
+    piece count, another length."""
+    w = window16()
+    attempt = 0
+    while True:
+        Z = np.random.default_rng([11, t, attempt]).integers(1, 256, 60, dtype=np.uint8)
+        Z[60 - t:] = 0
+        a, b = np.concatenate([w, Z]), np.concatenate([w, Z[:60 - t]])
+        if only_w_candidate(a, 0) and only_w_candidate(b, 0):
+            return a, b
+        attempt += 1
+
+
+@pytest.mark.parametrize("t", [1, 3, 11])
+def test_fp_length_only(S, torch, gpu_ctx, t):
+    params = (32, FP_AVG, 60)
+    objs = length_case(t)
+    want = restate(S, objs, params)
+    assert want == S.ChunkResult(2 * 92 - t, 4, 3, 32 + 60 + 60 - t, 2, 1)
+    with gpu_ctx.chunker(*params) as h:
+        for k, o in enumerate(objs):
+            h.add(dev(torch, np.concatenate([o, np.full(16 + -len(o) % 16, 0xB1 + k, np.uint8)])), len(o))
+        got = h.result()
+    assert got == want
+
+
+# ---- 12. pass C: one chunk far above 65 536 bytes -------------------------------------------------------
+
+def test_fp_chunk_of_megabytes(S, torch, gpu_ctx):
+    """Three objects of 4 MiB + 5 at avg = 2^24, max = 2^30: a wave walks 65 536 bitmap
+    words in pass B and 4096 laps in pass C; one flipped bit at 3 MiB + 7 is seen."""
+    params = (32, 1 << 24, 1 << 30)
+    size = 4 * MiB + 5
+    a = random_bytes(size, 90)
+    b = a.copy()
+    b[3 * MiB + 7] ^= 0x10
+    objs = [a, b, a]
+    want = restate(S, objs, params)
+    assert want.chunks % 3 == 0 and want.unique_chunks == want.chunks // 3 + 1      # one chunk holds the flip
+    assert want.bytes > MiB * want.chunks                                           # chunks of megabytes
+    with gpu_ctx.chunker(*params) as h:
+        for k, o in enumerate(objs):
+            h.add(dev(torch, np.concatenate([o, np.full(11, 0x21 + k, np.uint8)])), size)
+        got = h.result()
+    assert got == want
+
+
+# ---- 13. accumulation -----------------------------------------------------------------------------
 
 def test_adds_accumulate(S, torch, gpu_ctx):
     size, n, stride = 30011, 4, 30016
@@ -495,7 +728,7 @@ def test_array_growth(S, torch, gpu_ctx):
     assert sum(n // 32 + 2 for n in sizes) > 8 * 4096       # slots: at least three doublings from 4096
 
 
-# ---- 9. host form -----------------------------------------------------------------------------------
+# ---- 14. host form ----------------------------------------------------------------------------------
 
 def test_host_buffers(S):
     a = random_bytes(MiB + 5)
@@ -526,7 +759,7 @@ def test_host_buffer_across_the_copy_edge(S):
     assert S.measure_chunks_data(b[1:]) == want          # unaligned: the edge falls elsewhere in the caller's memory
 
 
-# ---- 10. refusals ------------------------------------------------------------------------------------
+# ---- 15. refusals ------------------------------------------------------------------------------------
 
 def test_refusals(S, torch, gpu_ctx):
     t = torch.zeros(3 * 4096 + 32, dtype=torch.uint8, device="cuda:0")
