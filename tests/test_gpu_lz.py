@@ -11,6 +11,7 @@ import threading
 import numpy as np
 import pytest
 
+import lz_cases as K
 import lz_restatement as R
 
 pytestmark = pytest.mark.gpu
@@ -178,6 +179,7 @@ def test_repeat_at_distance(S, torch, gpu_ctx, dist):
     """The table sees earlier groups only; the restatement says which repeats are found."""
     rng = np.random.default_rng(400 + dist)
     n = min(dist + 8 + 30, 65536)
+    ran = 0
     for start in (0, 3):
         if start + dist + 8 > n:
             continue
@@ -185,7 +187,18 @@ def test_repeat_at_distance(S, torch, gpu_ctx, dist):
         s = rng.integers(0, 256, 8, dtype=np.uint8)
         a[start:start + 8] = s
         a[start + dist:start + dist + 8] = s
-        check(gpu_ctx, torch, a, 65536, (dist, start))
+        want = check(gpu_ctx, torch, a, 65536, (dist, start))
+        ran += 1
+        # Which distances hold a match at all.  63, 64, 65 and 4096 do, with the distance as the
+        # offset (from the repeat's first byte, or a few bytes late where the source shares the
+        # repeat's group or a colliding position displaced its entry).  1 and 65 528 do not, and
+        # both parse as one literal run: at distance 1 the second write overlaps the first, so the
+        # block holds nine random bytes and no repeat; at 65 528 the repeat starts at n - 8,
+        # behind the last permitted match start n - 12 (and start = 3 does not fit the block).
+        offsets = [off for _, off, _ in K.triples(R.parse_block(a))]
+        assert (dist in offsets) == (dist in (63, 64, 65, 4096)), (dist, start)
+        assert (want["matches"] >= 1) == (dist in (63, 64, 65, 4096)), (dist, start)
+    assert ran == (1 if dist == 65528 else 2)
     found = {d: want_of([_repeat_block(d)], 65536)["matches"] for d in (63, 64, 65)}
     assert found[65] >= 1        # a whole group apart: always seen
 
@@ -262,7 +275,10 @@ LENGTHS = [14, 15, 269, 270, 524, 525]
 
 
 def test_every_length_step(S, torch, gpu_ctx):
-    """Literal runs and match lengths on both sides of every ext step."""
+    """Literal runs of 14, 15, 269, 270, 524 and 525 bytes lie on both sides of every step of
+    ext(lit).  The match lengths are the same six numbers, and those straddle no step of
+    ext(L - 4), which steps at L = 18 / 19, 273 / 274 and 528 / 529: test_every_match_length
+    holds those."""
     rng = np.random.default_rng(504)
     for x in LENGTHS:
         # a source, a first match, then x literals (a stop byte and x - 1 more) and a match of x;
@@ -586,3 +602,149 @@ def test_refusals(S, torch, gpu_ctx):
     for bb in (0, 4095, 8191, 69632, 131072):
         with pytest.raises(ValueError, match="block_bytes must be a multiple of 4096 from 4096 to 65536"):
             gpu_ctx.lz_measurer(bb)
+
+
+# ---- 8. every match length ---------------------------------------------------------------------------
+
+def sweep(ctx, torch, cases, bb=BLK):
+    """Crafted blocks of one size as one strided stream with poisoned gaps, one call; the sum
+    against the restatement's.  Only a wrong sum measures them one by one, to name the first."""
+    size = cases[0].block.size
+    assert all(c.block.size == size for c in cases) and size <= bb
+    stride = size + -size % 16 + 16
+    buf = strided([c.block for c in cases], stride, 0xEE)
+    got = R.as_dict(ctx.measure_lz_stream(dev(torch, buf), size, len(cases), stride, block_bytes=bb))
+    want = K.total(cases)
+    assert want["blocks"] == len(cases) and want["matches"] >= len(cases)
+    if got != want:
+        for c in cases:
+            one = R.as_dict(ctx.measure_lz(dev(torch, c.block), size, block_bytes=bb))
+            assert one == K.result(c.parse), f"first wrong case: {c.name}, match {c.triple}"
+        raise AssertionError(f"every case alone is right, the stream's sum is not: {got} != {want}")
+    return want
+
+
+def test_every_match_length(S, torch, gpu_ctx):
+    """L = 4..1030 ended by a differing byte: every (step, lane, count) at which the extension
+    loop can end in steps 0 to 2, and step 4; both sides of ext(L - 4)'s steps at 18 / 19,
+    273 / 274 and 528 / 529."""
+    cases = K.mismatch_sweep()
+    lengths = [c.triple[2] for c in cases]
+    assert lengths == list(range(4, 1031))
+    assert {18, 19, 273, 274, 528, 529, 256, 512, 768, 1024} <= set(lengths)
+    for c in cases[::97]:        # the judge itself, on a few: the cached parse is the restatement's
+        assert K.result(c.parse) == want_of([c.block], BLK)
+    sweep(gpu_ctx, torch, cases)
+
+
+def test_every_match_length_to_the_block_end(S, torch, gpu_ctx):
+    """L = 7..1030 with the copy equal through the block's last byte: the clamp at maxL in every
+    lane and count, and at maxL = 256, 512, 768 and 1024 the exit that flags no lane."""
+    cases = K.block_end_sweep()
+    assert [c.triple[2] for c in cases] == list(range(7, 1031))
+    for c in cases:
+        start, off, L = c.triple
+        assert start + L == c.block.size - 5 and c.block[-1] == c.block[-1 - off]
+    sweep(gpu_ctx, torch, cases)
+
+
+def test_match_ended_among_the_last_five_bytes(S, torch, gpu_ctx):
+    """The copy goes on for 0 to 4 bytes behind n - 5 and then differs: the extension's last
+    lane holds equal bytes past maxL, which must not count, at every place of its dword."""
+    cases = K.last_five_sweep()
+    assert len(cases) == 710
+    assert all(c.triple[0] + c.triple[2] == c.block.size - 5 for c in cases)
+    sweep(gpu_ctx, torch, cases)
+
+
+def test_short_matches_at_every_alignment(S, torch, gpu_ctx):
+    """L = 4..40 at all 16 pairs of (match start mod 4, source mod 4): both funnel shifts."""
+    cases = K.dense_sweep()
+    assert len({(c.triple[2], c.triple[0] % 4, (c.triple[0] - c.triple[1]) % 4) for c in cases}) == 37 * 16
+    sweep(gpu_ctx, torch, cases)
+
+
+# ---- 9. offsets ------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("k", range(13))
+def test_far_match(S, torch, gpu_ctx, k):
+    """Offsets up to the greatest there is (65 524: source at 0, match at n - 12 of a 65 536-byte
+    block), sources at 2^15 - 2 .. 2^15 and above, far matches of 256, 257, 4000 and 4096 bytes."""
+    cases = K.far_cases()
+    assert len(cases) == 13
+    c = cases[k]
+    assert c.triple in K.triples(c.parse), c.name        # the far match is in the parse
+    if k < 2:
+        assert c.triple == (c.block.size - 12, c.block.size - 12, 7)
+    want = check(gpu_ctx, torch, c.block, 65536, c.name)
+    assert want == K.result(c.parse)
+
+
+# ---- 10. the table -----------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("k", [3, 5, 16])
+def test_same_hash_group(S, torch, gpu_ctx, k):
+    """k words of one hash in one group: the last one's repeat is found at its first byte, every
+    other one's a byte late."""
+    cases = K.table_cases()["groups"][k]
+    wants = [check(gpu_ctx, torch, c.block, BLK, c.name) for c in cases]
+    assert all(w["matches"] == 1 for w in wants)
+    assert [w["match_bytes"] for w in wants] == [wants[-1]["match_bytes"] - 1] * (k - 1) + [K.TABLE_L]
+
+
+def test_chained_hash_pair(S, torch, gpu_ctx):
+    """Two overlapping words of one hash: the first leaves its entry to the second inside a
+    group, and enters itself at lane 63."""
+    inside, edge_later, edge_same = K.table_cases()["chained"]
+    wants = [check(gpu_ctx, torch, c.block, BLK, c.name) for c in (inside, edge_later, edge_same)]
+    assert [w["matches"] for w in wants] == [1, 1, 1]
+    assert [c.triple[2] for c in (inside, edge_later, edge_same)] == [15, 15, 8]      # late, late, at once
+    assert [w["match_bytes"] for w in wants] == [15, 15, 8]
+
+
+def test_source_at_every_lane(S, torch, gpu_ctx):
+    cases = K.source_at_every_lane()
+    found = [c for c in cases if c.triple in K.triples(c.parse)]
+    assert len(found) == 128 and [c.triple[0] - c.triple[1] for c in found] == list(range(128))
+    sweep(gpu_ctx, torch, cases)
+    for q in (0, 1, 62, 63, 64, 127):        # and alone, so a wrong one has a name
+        check(gpu_ctx, torch, cases[q].block, BLK, q)
+
+
+# ---- 11. a wave's later blocks -------------------------------------------------------------------------
+
+def reuse_objects(bb):
+    """Seven distinct objects of two full blocks and a ragged one, every block half bytes of 4
+    values and half random."""
+    rng = np.random.default_rng(900 + bb)
+    return [np.concatenate(low_entropy_objs(rng, 2, bb) + low_entropy_objs(rng, 1, 1000)) for _ in range(7)]
+
+
+@pytest.mark.parametrize("bb", BLOCK_BYTES)
+def test_wave_takes_later_blocks(S, torch, gpu_ctx, bb):
+    """More than three blocks for every wave of the grid, its successive blocks of different
+    content and length: the table clear and the staging over the previous block's LDS."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    grid = cus * min(32, (160 << 10) // (bb + (8 << 10)))
+    size = 2 * bb + 1000
+    n_objs = grid + 7
+    blocks = 3 * n_objs
+    assert blocks > 3 * grid
+    # block i is block i % 3 of object i // 3, a copy of object (i // 3) % 7
+    i = np.arange(blocks)
+    content = (i // 3) % 7 * 3 + i % 3
+    ragged = i % 3 == 2
+    assert (content[:-grid] != content[grid:]).all()              # blocks w and w + grid, every w
+    assert (~ragged[:-grid] & ragged[grid:]).any() and (ragged[:-grid] & ~ragged[grid:]).any()
+    objs = reuse_objects(bb)
+    distinct = {o[lo:lo + bb].tobytes() for o in objs for lo in range(0, size, bb)}
+    assert len(distinct) == 21 and all(o.size == size for o in objs)
+    per = [want_of([o], bb) for o in objs]
+    assert all(p["blocks"] == 3 and p["matches"] > 100 for p in per)
+    counts = np.bincount(np.arange(n_objs) % 7, minlength=7)
+    want = {k: int(sum(int(c) * p[k] for c, p in zip(counts, per))) for k in R.FIELDS}
+    stride = size + -size % 16 + 16
+    buf = strided([objs[j % 7] for j in range(n_objs)], stride, 0x3C)
+    got = gpu_ctx.measure_lz_stream(dev(torch, buf), size, n_objs, stride, block_bytes=bb)
+    assert R.as_dict(got) == want
+    assert got.blocks == blocks

@@ -3,9 +3,10 @@ restatement of the definition (tests/lz_restatement.py) yields valid LZ4 blocks
 of exactly the stated size, the cross-check numbers of the definition, the
 reference's compress contract through the restatement, the C calls' argument
 checks (a C program), the Python call's buffer handling, LzResult's derived
-values, and the plan (csrc/s3dg_lz_plan.h over csrc/s3dg_span_plan.h, compiled
+values, the plan (csrc/s3dg_lz_plan.h over csrc/s3dg_span_plan.h, compiled
 with g++ alone, plain and under the address and undefined-behaviour
-sanitizers) over a sweep of its inputs."""
+sanitizers) over a sweep of its inputs, and the crafted cases of
+tests/lz_cases.py: each contains the match it is built for."""
 import dataclasses
 import os
 import shutil
@@ -14,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import lz_cases as K
 import lz_restatement as R
 from oracle import oracle_c as C
 from oracle import oracle_py as P
@@ -80,6 +82,79 @@ def test_short_blocks_round_trip(n):
     assert z.matches == (1 if n >= 13 else 0)
     roundtrip(rng.integers(0, 256, n, dtype=np.uint8))
     roundtrip(rng.integers(0, 2, n, dtype=np.uint8))
+
+
+# ---- the crafted cases of the GPU tests mean what they say --------------------------
+
+def test_crafted_cases_parse_as_meant():
+    """Every case of every builder of tests/lz_cases.py holds its intended
+    (match start, offset, L), encodes to `size` bytes and decodes to itself; no
+    length, alignment pair, lane or word is left out."""
+    mismatch, block_end, dense = K.mismatch_sweep(), K.block_end_sweep(), K.dense_sweep()
+    far, table, lanes = K.far_cases(), K.table_cases(), K.source_at_every_lane()
+    groups = [c for cs in table["groups"].values() for c in cs]
+    last_five = K.last_five_sweep()
+    every = [*mismatch, *block_end, *dense, *last_five, *far, *groups, *table["chained"], *lanes]
+    for c in every:
+        assert c.triple in K.triples(c.parse), c.name
+        assert not c.block.flags.writeable
+        start, off, L = c.triple
+        assert L >= 4 and 1 <= off <= start and start + L <= c.block.size - 5, c.name
+        assert bytes(c.block[start:start + L]) == bytes(c.block[start - off:start - off + L]), c.name
+        raw = bytes(c.block)
+        enc = R.encode(raw, c.parse)
+        assert len(enc) == c.parse.size and R.decode(enc) == raw, c.name
+        assert K.result(c.parse) == R.measure([c.block], 65536), c.name
+    # the counts: nothing left out
+    assert [c.triple[2] for c in mismatch] == list(range(4, 1031)) and len(mismatch) == 1027
+    assert [c.triple[2] for c in block_end] == list(range(7, 1031)) and len(block_end) == 1024
+    for c in mismatch + dense:          # ended by a differing byte, short of the block's end
+        start, off, L = c.triple
+        assert start + L < c.block.size - 5 and c.block[start + L] != c.block[start - off + L], c.name
+        assert start // 64 > (start - off) // 64
+    for c in block_end:                 # equal through the last byte
+        start, off, L = c.triple
+        n = c.block.size
+        assert start + L == n - 5 and bytes(c.block[start:]) == bytes(c.block[start - off:n - off]), c.name
+    # a differing byte among the last five: equal bytes behind n - 5 that do not count, at every
+    # place of the extension's last dword
+    assert len(last_five) == 5 * len(K.LENGTHS_LAST_FIVE) == 710
+    for c in last_five:
+        start, off, L = c.triple
+        n = c.block.size
+        j = int(np.nonzero(c.block[start + L:] != c.block[start + L - off:n - off])[0][0])
+        assert start + L == n - 5 and c.name.endswith(f"j={j}"), c.name
+    assert {(c.triple[2] % 4, int(c.name[-1])) for c in last_five} == {(r, j) for r in range(4) for j in range(5)}
+    pairs = {}
+    for c in dense:
+        start, off, L = c.triple
+        pairs.setdefault(L, set()).add((start % 4, (start - off) % 4))
+    assert sorted(pairs) == list(range(4, 41)) and all(len(v) == 16 for v in pairs.values())
+    assert len(dense) == 37 * 16
+    # the ends of the extension loop: every (step, lane, count) of steps 0 to 2, and step 4
+    ends = {(L // 256, L % 256 // 4, L % 4) for L in (c.triple[2] for c in mismatch)}
+    assert {(t, f, k) for t in range(3) for f in range(64) for k in range(4)} - {(0, 0, k) for k in range(4)} <= ends
+    assert (4, 0, 0) in ends
+    # both sides of every step of ext(L - 4) below 1031
+    assert [R.ext(L - 4) for L in (18, 19, 273, 274, 528, 529, 783, 784)] == [0, 1, 1, 2, 2, 3, 3, 4]
+    # offsets: the greatest of a 65536- and a 65535-byte block, sources from 2^15 on
+    assert far[0].triple == (65524, 65524, 7) and far[1].triple == (65523, 65523, 7)
+    assert K.triples(far[0].parse) == [(13, 1, 65511), (65524, 65524, 7)]
+    srcs = [c.triple[0] - c.triple[1] for c in far]
+    assert {32766, 32767, 32768} <= set(srcs) and max(srcs) > 65000
+    assert {256, 257, 4000, 4096} <= {c.triple[2] for c in far if c.triple[1] > 60000}
+    # the table: one found byte less for every word but the group's last
+    for k, cs in table["groups"].items():
+        assert len(cs) == k and all(c.parse.matches == 1 for c in cs)
+        assert [c.parse.match_bytes for c in cs] == [K.TABLE_L - 1] * (k - 1) + [K.TABLE_L]
+    assert [c.parse.match_bytes for c in table["chained"]] == [15, 15, 8]
+    assert [c.triple[0] - c.triple[1] for c in lanes] == list(range(128))
+    assert all(c.triple[0] >= 192 for c in lanes)
+    for name, cs in (("mismatch", mismatch), ("block end", block_end), ("dense", dense),
+                     ("last five", last_five), ("far", far),
+                     ("table", groups + list(table["chained"])), ("lanes", lanes)):
+        print(f"{name}: {len(cs)} cases, worst seed index {K.worst_seed(cs)}")
+    assert K.worst_seed(every) < K.SEEDS
 
 
 # ---- the definition's cross-check numbers ------------------------------------------
