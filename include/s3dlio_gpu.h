@@ -411,6 +411,51 @@ int s3dg_measure_add_range(s3dg_measure *m, const void *src, uint64_t obj_size,
  * and fills *out.  The handle is unchanged: get again, or add and get.  An
  * empty handle yields all zeros. */
 int s3dg_measure_get(s3dg_measure *m, s3dg_measure_result *out);
+/* A mixed-size batch in one add: span k is one object of
+ * `size` bytes at src_base + off, measured from its own first byte.  The
+ * handles of the three read-only analyses take it:
+ *   s3dg_measure_add_batch  adds exactly the sum over k of
+ *                           s3dg_measure_add_range(src_base + off_k, size_k, 0, all blocks),
+ *   s3dg_lz_add_batch       the same sum of s3dg_lz_add_range,
+ *   s3dg_chunks_add_batch   the sum of s3dg_chunks_add_stream(src_base + off_k, size_k, size_k, 1).
+ * Blocks and chunks never cross objects; a ragged last block is finalised
+ * with its length.  unique_* stays exact over everything the handle has seen:
+ * batch adds, stream adds and range adds mixed.
+ * Layout (as s3dg_verify_controlled_batch): spans may come in any order, leave
+ * gaps, overlap and repeat.  Two spans over the same bytes are two objects:
+ * bytes and blocks (chunks) count twice, unique_* does not.  Empty spans
+ * (size == 0) are allowed anywhere, whatever their off, and contribute
+ * nothing: no block, no chunk, no slot.
+ * Reading: a 16-byte piece is loaded whole only when it ends at or below its
+ * object's length, the ragged piece byte by byte; no byte of a gap is ever
+ * read, nor any byte before src_base + off or at or past off + size.
+ * Asynchronous on `stream` and ordered like s3dg_*_add_stream: a later launch
+ * on the same stream may overwrite the payload.  `spans` is consumed before
+ * the call returns: the caller may free or rewrite it at once.  Slots and
+ * scratch are reserved on the host under the handle's mutex, so adds from
+ * several threads on several streams are safe.  Per add and stream the table
+ * of the spans is built on the host and uploaded: 40 bytes per non-empty span
+ * and 32 bytes per tile of 2..64 4 KiB granules of an object (the tile size
+ * follows s3dg_set_batch_tile as in the batch verify; results are identical at
+ * every size), in pinned host memory and in device memory.
+ * Refusals (S3DG_EINVAL, each with its message; every span is checked before
+ * anything is reserved or enqueued, so a refused add leaves the handle exactly
+ * as it was): a null handle; null `spans` with n > 0 ("null span array"); a
+ * null or not 16-byte aligned src_base; a non-empty span whose off is not a
+ * multiple of 16 ("off must be a multiple of 16") or which is larger than
+ * 2^31 x 4096 bytes ("object larger than 2^31 blocks"), the message naming
+ * the first offending index ("span 7: ..."); more than 2^40 granules or
+ * 2^31 - 1 chunk slots in one add, and the handles' own caps with their
+ * messages.  n == 0, or only empty spans, launches nothing and is accepted
+ * whatever src_base.
+ * A handle created with S3DG_MEASURE_HIST takes the histogram of the spans'
+ * bytes too. */
+typedef struct {
+    uint64_t off;    /* bytes from src_base */
+    uint64_t size;   /* bytes */
+} s3dg_span;
+int s3dg_measure_add_batch(s3dg_measure *m, const void *src_base, const s3dg_span *spans, uint64_t n,
+                           void *stream);
 /* A host buffer (any alignment, read-only memory included) as one object,
  * on a host slot's GPU: copied in chunks of whole blocks (up to 64 MiB; one
  * block per chunk, in two buffers of the call's own, when block_bytes is
@@ -484,6 +529,12 @@ int s3dg_chunks_reset(s3dg_chunks *h);   /* waits for the enqueued adds; an empt
  * nothing. */
 int s3dg_chunks_add_stream(s3dg_chunks *h, const void *src, uint64_t obj_size, uint64_t stride,
                            uint64_t n_objs, void *stream);
+/* A mixed-size batch in one add: the contract of s3dg_measure_add_batch.  Every
+ * span is chunked on its own from its first byte; the add equals the sum of
+ * s3dg_chunks_add_stream(src_base + off_k, size_k, size_k, 1) over the spans.
+ * A span takes ceil(size / min_bytes) + 1 record slots. */
+int s3dg_chunks_add_batch(s3dg_chunks *h, const void *src_base, const s3dg_span *spans, uint64_t n,
+                          void *stream);
 /* Waits for the enqueued adds, counts the distinct fingerprints on a copy and
  * fills *out.  The handle is unchanged: get again, or add and get.  An empty
  * handle yields all zeros. */
@@ -571,6 +622,10 @@ int s3dg_lz_add_stream(s3dg_lz *h, const void *src, uint64_t obj_size, uint64_t 
  * ranges that add up to the object give the object's result exactly. */
 int s3dg_lz_add_range(s3dg_lz *h, const void *src, uint64_t obj_size, uint64_t blk_lo,
                       uint64_t blk_hi, void *stream);
+/* A mixed-size batch in one add: the contract of s3dg_measure_add_batch.  Every
+ * span is cut into blocks from its own first byte; the add equals the sum of
+ * s3dg_lz_add_range(src_base + off_k, size_k, 0, all blocks) over the spans. */
+int s3dg_lz_add_batch(s3dg_lz *h, const void *src_base, const s3dg_span *spans, uint64_t n, void *stream);
 /* Waits for the enqueued adds and fills *out.  The handle is unchanged: get
  * again, or add and get.  An empty handle yields all zeros. */
 int s3dg_lz_get(s3dg_lz *h, s3dg_lz_result *out);

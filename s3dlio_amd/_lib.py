@@ -53,6 +53,11 @@ class VerifyRec(ctypes.Structure):
     _fields_ = [("mismatched_bytes", c_u64), ("mismatched_blocks", c_u64), ("first_offset", c_u64)]
 
 
+class Span(ctypes.Structure):
+    """s3dg_span"""
+    _fields_ = [("off", c_u64), ("size", c_u64)]
+
+
 class MeasureRec(ctypes.Structure):
     """s3dg_measure_result"""
     _fields_ = [("bytes", c_u64), ("zero_bytes", c_u64), ("blocks", c_u64), ("unique_blocks", c_u64),
@@ -127,12 +132,14 @@ SIGNATURES = {
     "s3dg_measure_reset": (c_int, [c_vp]),
     "s3dg_measure_add_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp]),
     "s3dg_measure_add_range": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp]),
+    "s3dg_measure_add_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(Span), c_u64, c_vp]),
     "s3dg_measure_get": (c_int, [c_vp, ctypes.POINTER(MeasureRec)]),
     "s3dg_measure_data": (c_int, [c_vp, c_u64, c_u64, c_int, ctypes.POINTER(MeasureRec)]),
     "s3dg_chunks_create": (c_int, [c_vp, c_u64, c_u64, c_u64, ctypes.POINTER(c_vp)]),
     "s3dg_chunks_destroy": (c_int, [c_vp]),
     "s3dg_chunks_reset": (c_int, [c_vp]),
     "s3dg_chunks_add_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp]),
+    "s3dg_chunks_add_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(Span), c_u64, c_vp]),
     "s3dg_chunks_get": (c_int, [c_vp, ctypes.POINTER(ChunkRec)]),
     "s3dg_chunks_set_option": (c_int, [c_vp, c_int, c_int]),
     "s3dg_chunks_pass_seconds": (c_int, [c_vp, ctypes.POINTER(ctypes.c_double)]),
@@ -142,6 +149,7 @@ SIGNATURES = {
     "s3dg_lz_reset": (c_int, [c_vp]),
     "s3dg_lz_add_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp]),
     "s3dg_lz_add_range": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp]),
+    "s3dg_lz_add_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(Span), c_u64, c_vp]),
     "s3dg_lz_get": (c_int, [c_vp, ctypes.POINTER(LzRec)]),
     "s3dg_lz_data": (c_int, [c_vp, c_u64, c_u64, ctypes.POINTER(LzRec)]),
     "s3dg_write_ceiling": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),

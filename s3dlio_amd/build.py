@@ -36,6 +36,7 @@ HEADERS = [os.path.join(CSRC, "s3dg_internal.h"), os.path.join(CSRC, "s3dg_ctx.h
            os.path.join(CSRC, "s3dg_chunk_plan.h"), os.path.join(CSRC, "s3dg_chunks.h"),
            os.path.join(CSRC, "s3dg_lz_plan.h"), os.path.join(CSRC, "s3dg_lz.h"),
            os.path.join(CSRC, "s3dg_verify_batch_plan.h"), os.path.join(CSRC, "s3dg_span_plan.h"),
+           os.path.join(CSRC, "s3dg_span_batch_plan.h"),
            os.path.join(CSRC, "s3dg_accum.h"),
            os.path.join(ROOT, "include", "s3dlio_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

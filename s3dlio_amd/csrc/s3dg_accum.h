@@ -17,6 +17,11 @@ namespace s3dg {
 // arrays and totals.  A handle with scratch per stream derives from this.
 struct AccumStream {
     hipEvent_t ev = nullptr;
+    // a batch add's span table (s3dg_span_batch_plan.h): built in `stage`
+    // (pinned), uploaded to `table`; up = the latest upload out of `stage`
+    void *stage = nullptr, *table = nullptr;
+    uint64_t stage_cap = 0, table_cap = 0;
+    hipEvent_t up = nullptr;
 };
 
 // Handle entry points: a null handle is an error; one call at a time per
@@ -33,6 +38,20 @@ struct AccumStream {
         hipError_t e_ = (expr);                                    \
         if (e_ != hipSuccess) return hip_failed(e_, op, what);     \
     } while (0)
+
+// *buf holds `need` bytes; its contents are not kept.  It is replaced only
+// after `ev` (the latest user of the old one; null: it is idle).
+inline int accum_regrow(void **buf, uint64_t *cap, uint64_t need, hipEvent_t ev, const char *wait_what,
+                        const char *malloc_what) {
+    if (need <= *cap) return S3DG_OK;
+    if (ev) HIP_TRY(hipEventSynchronize(ev), wait_what);
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    HIP_TRY(hipMalloc(buf, need), malloc_what);
+    *cap = need;
+    return S3DG_OK;
+}
 
 template <class Stream = AccumStream>
 struct Accum {
@@ -92,6 +111,35 @@ struct Accum {
         return S3DG_OK;
     }
 
+    // A batch add's table on stream s, in two steps.  table_stage: S's pinned
+    // buffer holds `bytes`, idle (a later add on the stream reuses it, so the
+    // earlier upload is waited for), for the caller to build the table in.
+    // table_upload: its copy into S's device buffer, enqueued on s behind the
+    // stream's earlier adds, which read the old table.
+    int table_stage(Stream &S, uint64_t bytes, void **host) {
+        if (!S.up) HIP_TRY(hipEventCreateWithFlags(&S.up, hipEventDisableTiming), "hipEventCreate");
+        else ACCUM_TRY(hipEventSynchronize(S.up), "hipEventSynchronize", " table upload");
+        if (bytes > S.stage_cap) {
+            if (S.stage) (void)hipHostFree(S.stage);
+            S.stage = nullptr;
+            S.stage_cap = 0;
+            const uint64_t cap = span_grow_cap(S.stage_cap, bytes);
+            ACCUM_TRY(hipHostMalloc(&S.stage, cap, hipHostMallocDefault), "hipHostMalloc", " table");
+            S.stage_cap = cap;
+        }
+        *host = S.stage;
+        return S3DG_OK;
+    }
+    int table_upload(Stream &S, uint64_t bytes, hipStream_t s) {
+        // the stream's earlier add may still read the old table
+        if (int r = accum_regrow(&S.table, &S.table_cap, span_grow_cap(S.table_cap, bytes), S.ev,
+                                 "hipEventSynchronize(add)", "hipMalloc(span table)"))
+            return r;
+        ACCUM_TRY(hipMemcpyAsync(S.table, S.stage, bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync", " table");
+        ACCUM_TRY(hipEventRecord(S.up, s), "hipEventRecord", " table upload");
+        return S3DG_OK;
+    }
+
     int reset_totals() {
         if (int r = wait_adds()) return r;
         ACCUM_TRY(hipMemsetAsync(tot, 0, tot_words * sizeof(uint64_t), gs), "hipMemsetAsync", " totals");
@@ -138,20 +186,6 @@ struct Accum {
     }
 };
 
-// *buf holds `need` bytes; its contents are not kept.  It is replaced only
-// after `ev` (the latest user of the old one; null: it is idle).
-inline int accum_regrow(void **buf, uint64_t *cap, uint64_t need, hipEvent_t ev, const char *wait_what,
-                        const char *malloc_what) {
-    if (need <= *cap) return S3DG_OK;
-    if (ev) HIP_TRY(hipEventSynchronize(ev), wait_what);
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    HIP_TRY(hipMalloc(buf, need), malloc_what);
-    *cap = need;
-    return S3DG_OK;
-}
-
 // s3dg_*_destroy: under the handle's lock with its device current, every
 // stream's event waited for and destroyed (then per_stream(S) for what else
 // the stream owns), the handle's stream drained and destroyed, arrays() for
@@ -166,6 +200,9 @@ int accum_destroy(H *h, const char *null_text, PerStream per_stream, Arrays arra
                 (void)hipEventSynchronize(kv.second.ev);
                 (void)hipEventDestroy(kv.second.ev);
             }
+            if (kv.second.up) (void)hipEventDestroy(kv.second.up);   // the upload precedes the add just waited for
+            if (kv.second.stage) (void)hipHostFree(kv.second.stage);
+            if (kv.second.table) (void)hipFree(kv.second.table);
             per_stream(kv.second);
         }
         if (h->gs) {

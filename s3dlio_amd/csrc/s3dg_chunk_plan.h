@@ -49,7 +49,17 @@ struct ChunkPlan {
     // the stream's scratch: [bitmap | record offsets (8 B) | record lengths (4 B) | chunk counts (4 B per
     // object) | candidate counts (4 B per granule)]
     uint64_t off_offset, len_offset, cnt_offset, gcnt_offset, scratch_bytes;
+    uint64_t own_offset;     // a batch add: behind those, the object of every record slot (4 B per slot)
 };
+
+// The scratch offsets of a plan whose n_objs, granules and slots are set.
+inline void chunk_plan_scratch(ChunkPlan *P) {
+    P->off_offset = P->granules * 512;                               // a multiple of 256
+    P->len_offset = P->off_offset + span_align256(P->slots * 8);
+    P->cnt_offset = P->len_offset + span_align256(P->slots * 4);
+    P->gcnt_offset = P->cnt_offset + span_align256(P->n_objs * 4);
+    P->scratch_bytes = P->gcnt_offset + span_align256(P->granules * 4);
+}
 
 // s3dg_chunks_add_stream's arguments (the refusals of
 // s3dg_measure_add_stream).  Returns null and fills *P, or the refusal's text.
@@ -75,12 +85,23 @@ inline const char *chunk_plan_stream(ChunkPlan *P, uint64_t src, uint64_t obj_si
     P->granules = n_objs * gpo;
     P->nx = span_nx(gpo);
     P->ny = span_ny(n_objs);
-    P->off_offset = P->granules * 512;                               // a multiple of 256
-    P->len_offset = P->off_offset + span_align256(P->slots * 8);
-    P->cnt_offset = P->len_offset + span_align256(P->slots * 4);
-    P->gcnt_offset = P->cnt_offset + span_align256(n_objs * 4);
-    P->scratch_bytes = P->gcnt_offset + span_align256(P->granules * 4);
+    chunk_plan_scratch(P);
     return nullptr;
+}
+
+// A batch add (s3dg_span_batch_plan.h) of `live` non-empty spans with the
+// sums of their granules, record slots and bytes: the same scratch, the
+// objects' parts at their prefix sums.  len, gpo, wpo, rpo, nx and ny stay
+// zero: the objects differ and the granule pass is cut by tiles.
+inline void chunk_plan_batch(ChunkPlan *P, uint64_t live, uint64_t granules, uint64_t slots, uint64_t bytes) {
+    *P = ChunkPlan{};
+    P->n_objs = live;
+    P->granules = granules;
+    P->slots = slots;
+    P->bytes = bytes;
+    chunk_plan_scratch(P);
+    P->own_offset = P->scratch_bytes;
+    P->scratch_bytes += span_align256(slots * 4);
 }
 
 // Sub-launch (ix, iy) of pass A: objects [y0, y0 + gy), granules [x0, x0 + gx).

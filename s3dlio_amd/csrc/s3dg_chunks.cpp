@@ -137,6 +137,48 @@ int s3dg_chunks_add_stream(s3dg_chunks *h, const void *src, uint64_t obj_size, u
     return add_plan(h, P, src, stride, (hipStream_t)stream);
 }
 
+int s3dg_chunks_add_batch(s3dg_chunks *h, const void *src_base, const s3dg_span *spans, uint64_t n, void *stream) {
+    ACCUM_SCOPE(h, kNullHandle);
+    hipStream_t s = (hipStream_t)stream;
+    SpanBatchCounts C;
+    std::string why;
+    if (!span_batch_check((uint64_t)(uintptr_t)src_base, spans, n, 0, h->min_bytes, &C, &why))
+        return fail(S3DG_EINVAL, why);
+    if (C.live == 0) return S3DG_OK;
+    if (h->used + C.slots > kChunkMaxSlots) return fail(S3DG_EINVAL, "more than 2^31 - 1 chunk slots in one handle");
+    if (int r = slots_reserve(h, h->used + C.slots)) return r;
+    ChunkStream *Sp = nullptr;
+    if (int r = h->stream_enter(s, &Sp)) return r;
+    ChunkStream &S = *Sp;
+    ChunkPlan P;
+    chunk_plan_batch(&P, C.live, C.granules, C.slots, C.bytes);
+    // the stream's earlier add may still use the old scratch
+    if (int r = accum_regrow(&S.scratch, &S.cap, P.scratch_bytes, S.ev, "hipEventSynchronize(chunks add)",
+                             "hipMalloc(chunk scratch)"))
+        return r;
+    const uint32_t tshift = span_batch_tile_shift(C, h->ctx->tile_shift);
+    const uint64_t ntiles = C.ntiles[tshift], tbytes = span_batch_table_bytes(C.live, ntiles);
+    void *host = nullptr;
+    if (int r = h->table_stage(S, tbytes, &host)) return r;
+    span_batch_build(spans, n, 0, h->min_bytes, tshift, (SpanEnt *)host,
+                     (SpanTile *)((uint8_t *)host + span_batch_tile_offset(C.live)));
+    if (int r = h->table_upload(S, tbytes, s)) return r;
+    const bool timing = h->timing;
+    if (timing)
+        for (int k = 0; k < 4; ++k)
+            if (!S.tev[k]) HIP_TRY(hipEventCreate(&S.tev[k]), "hipEventCreate");
+    HIP_TRY(launch_chunk_batch(P, (const uint8_t *)src_base, (const SpanEnt *)S.table,
+                               (const SpanTile *)((const uint8_t *)S.table + span_batch_tile_offset(C.live)), ntiles,
+                               tshift, 32 - h->bits, h->table, h->min_bytes, h->max_bytes, S.scratch, h->fp + h->used,
+                               h->flen + h->used, h->tot, timing ? S.tev : nullptr, s),
+            "launch chunk batch passes");
+    if (timing) h->timed = &S;
+    if (int r = h->stream_mark(S, s)) return r;
+    h->used += C.slots;
+    h->bytes += C.bytes;
+    return S3DG_OK;
+}
+
 int s3dg_chunks_get(s3dg_chunks *h, s3dg_chunk_result *out) {
     if (!out) return fail(S3DG_EINVAL, "null output");
     result_clear(out);

@@ -28,6 +28,14 @@ hipError_t launch_chunk_cuts(const ChunkPlan &P, uint64_t min_bytes, uint64_t ma
 // (flen 0: the slot holds no chunk).
 hipError_t launch_chunk_fingerprints(const ChunkPlan &P, const uint8_t *src, uint64_t stride, const void *scratch,
                                      MeasureFp *fp, uint32_t *flen, hipStream_t s);
+// The batch form of the three passes over an add's uploaded
+// table (s3dg_span_batch_plan.h): P from chunk_plan_batch; granule g of entry j
+// owns bitmap words from 64 (g0_j + g), entry j's records and slots start at
+// s0_j.  tev: null, or four events recorded around the passes.
+hipError_t launch_chunk_batch(const ChunkPlan &P, const uint8_t *src_base, const SpanEnt *ents, const SpanTile *tiles,
+                              uint64_t ntiles, uint32_t tshift, uint32_t shift, bool table, uint64_t min_bytes,
+                              uint64_t max_bytes, void *scratch, MeasureFp *fp, uint32_t *flen, uint64_t *tot,
+                              hipEvent_t *tev, hipStream_t s);
 // Distinct fingerprints among the n slots and the summed length of one chunk
 // each: two stable radix sorts of (key, slot index) in `work`
 // (chunk_sort_bytes(n) bytes, then *tmp_bytes of hipCUB scratch), added to

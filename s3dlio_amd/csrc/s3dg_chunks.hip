@@ -121,6 +121,92 @@ __global__ __launch_bounds__(64) void k_chunk_candidates(const uint8_t *src, uin
     if (lane == 0) gcnt[(uint64_t)blockIdx.y * gpo + g] = (uint32_t)c;
 }
 
+// k_chunk_candidates' granule for the batch form (the kernel above keeps its own
+// text: sharing this function changed the register allocation of its <false>
+// instantiation).  One granule by one wave: granule g of its object at bs (nothing before
+// granule 0 is read), `left` > 0 bytes from bs to the object's end; the
+// granule's 64 bitmap words from bitmap[w0] on and its number of candidates to
+// gcnt[gi].
+template <bool TAB>
+__device__ __forceinline__ void chunk_granule(const uint8_t *bs, uint32_t g, uint64_t left, uint32_t shift,
+                                              uint64_t *bitmap, uint64_t w0, uint32_t *gcnt, uint64_t gi) {
+    __shared__ uint32_t rows[65 * kRow];
+    __shared__ uint32_t gtab[TAB ? 256 : 1];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t L = left < kGran ? (uint32_t)left : kGran;
+    if constexpr (TAB) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gtab[lane + 64 * k] = gear(lane + 64 * k);
+    }
+    if (lane < 2) {   // row 0, bytes 32..63: the 32 bytes before the granule
+        u32x4 d = u32x4{0u, 0u, 0u, 0u};
+        if (g > 0) d = *reinterpret_cast<const u32x4 *>(bs - 32 + 16 * lane);
+        uint32_t *r = rows + 8 + 4 * lane;
+        r[0] = d.x; r[1] = d.y; r[2] = d.z; r[3] = d.w;
+    }
+    u32x4 D[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t o = (lane + 64 * k) * 16;
+        D[k] = u32x4{0u, 0u, 0u, 0u};
+        if (o + 16 <= L) D[k] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(bs + o));
+        else if (o < L) D[k] = load_piece(bs, o, L);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t q = lane + 64 * k;
+        uint32_t *r = rows + (1 + (q >> 2)) * kRow + (q & 3) * 4;
+        r[0] = D[k].x; r[1] = D[k].y; r[2] = D[k].z; r[3] = D[k].w;
+    }
+    __syncthreads();
+    auto G = [&](uint32_t b) -> uint32_t {
+        if constexpr (TAB) return gtab[b];
+        else return gear(b);
+    };
+    const uint32_t *prev = rows + lane * kRow, *own = prev + kRow;
+    uint32_t h = 0;
+#pragma unroll
+    for (int j = 8; j < 16; ++j) {
+        const uint32_t w = prev[j];
+#pragma unroll
+        for (int b = (j == 8 ? 1 : 0); b < 4; ++b) h = (h << 1) + G((w >> (8 * b)) & 0xFFu);
+    }
+    uint32_t m[2] = {0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const uint32_t w = own[j];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            h = (h << 1) + G((w >> (8 * b)) & 0xFFu);
+            m[j >> 3] |= (uint32_t)((h >> shift) == 0) << ((4 * j + b) & 31);
+        }
+    }
+    uint64_t bits = (uint64_t)m[0] | ((uint64_t)m[1] << 32);
+    if (g == 0 && lane == 0) bits &= ~0ull << 31;          // a window needs 32 bytes of the object
+    const uint32_t o = lane * 64;
+    if (o >= L) bits = 0;
+    else if (L - o < 64) bits &= ~0ull >> (64 - (L - o));  // nothing at or beyond the object's end
+    bitmap[w0 + lane] = bits;
+    const uint64_t c = wave_sum64((uint64_t)__builtin_popcountll(bits));
+    if (lane == 0) gcnt[gi] = (uint32_t)c;
+}
+
+// The batch form: k_measure_batch's 1D grid of tile slots.
+// Granule g of the add (its entry's g0 + its index in the object) owns bitmap
+// words [64 g, 64 g + 64) and gcnt[g]; a dead slot exits.
+template <bool TAB>
+__global__ __launch_bounds__(64) void k_chunk_candidates_batch(const uint8_t *src_base, const SpanTile *tiles,
+                                                               uint64_t tile0, uint32_t tshift, uint32_t shift,
+                                                               uint64_t *bitmap, uint32_t *gcnt) {
+    const uint32_t w = blockIdx.x;
+    const SpanTile T = tiles[tile0 + (w >> tshift)];
+    const uint32_t k = w & ((1u << tshift) - 1u);
+    const uint64_t o = (uint64_t)k * kGran;
+    if (o >= T.left) return;
+    chunk_granule<TAB>(src_base + T.off + o, T.first + k, T.left - o, shift, bitmap, (T.rec + k) * 64, gcnt,
+                       T.rec + k);
+}
+
 // *total += the sum of v[0, n): one vector atomic per workgroup.
 __global__ __launch_bounds__(256) void k_chunk_sum(const uint32_t *v, uint64_t n, uint64_t *total) {
     __shared__ uint64_t ws[4];
@@ -142,13 +228,11 @@ __global__ __launch_bounds__(256) void k_chunk_sum(const uint32_t *v, uint64_t n
 // and that word's lowest bit give the cut.  None: a forced cut at max bytes
 // when the object holds that many from s, else the object's end closes the
 // chunk.  Everything that steers the loop is wave-uniform.
-__global__ __launch_bounds__(256) void k_chunk_cuts(const uint64_t *bitmap, uint64_t n_objs, uint64_t len,
-                                                    uint64_t wpo, uint64_t rpo, uint64_t minb, uint64_t maxb,
-                                                    uint64_t *roff, uint32_t *rlen, uint32_t *cnt, uint64_t *tot) {
+// Object j of len bytes by one wave: its bitmap bm, its records from slot r0 on, its count to cnt[j].
+__device__ __forceinline__ void chunk_walk(const uint64_t *bm, uint64_t j, uint64_t len, uint64_t minb, uint64_t maxb,
+                                           uint64_t r0, uint64_t *roff, uint32_t *rlen, uint32_t *cnt,
+                                           uint64_t *tot) {
     const uint32_t lane = threadIdx.x & 63;
-    const uint64_t j = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (j >= n_objs) return;
-    const uint64_t *bm = bitmap + j * wpo;
     uint64_t s = 0, n = 0, forced = 0;
     while (s < len) {
         uint64_t e = len - 1;
@@ -182,8 +266,8 @@ __global__ __launch_bounds__(256) void k_chunk_cuts(const uint64_t *bitmap, uint
             }
         }
         if (lane == 0) {
-            roff[j * rpo + n] = s;
-            rlen[j * rpo + n] = (uint32_t)(e - s + 1);
+            roff[r0 + n] = s;
+            rlen[r0 + n] = (uint32_t)(e - s + 1);
         }
         ++n;
         s = e + 1;
@@ -193,6 +277,31 @@ __global__ __launch_bounds__(256) void k_chunk_cuts(const uint64_t *bitmap, uint
         atomic_add64(&tot[kChunkTotChunks], n);
         if (forced) atomic_add64(&tot[kChunkTotForced], forced);
     }
+}
+
+__global__ __launch_bounds__(256) void k_chunk_cuts(const uint64_t *bitmap, uint64_t n_objs, uint64_t len,
+                                                    uint64_t wpo, uint64_t rpo, uint64_t minb, uint64_t maxb,
+                                                    uint64_t *roff, uint32_t *rlen, uint32_t *cnt, uint64_t *tot) {
+    const uint64_t j = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= n_objs) return;
+    chunk_walk(bitmap + j * wpo, j, len, minb, maxb, j * rpo, roff, rlen, cnt, tot);
+}
+
+// The batch form: one wave per entry, with its own length, its bitmap at the
+// granule prefix and its records at the slot prefix.  It leaves its index in
+// own[] for every slot of the entry, so pass C finds a slot's object with one
+// load (a search per slot over the slot prefix cost pass C 4.2 ms against the
+// stream form's 2.3 on 1024 x 8 MiB).
+__global__ __launch_bounds__(256) void k_chunk_cuts_batch(const uint64_t *bitmap, const SpanEnt *ents, uint64_t live,
+                                                          uint64_t minb, uint64_t maxb, uint64_t *roff,
+                                                          uint32_t *rlen, uint32_t *cnt, uint32_t *own,
+                                                          uint64_t *tot) {
+    const uint64_t j = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= live) return;
+    const SpanEnt e = ents[j];
+    const uint64_t slots = (e.size + minb - 1) / minb + 1;   // span_obj_slots
+    for (uint64_t k = threadIdx.x & 63; k < slots; k += 64) own[e.s0 + k] = (uint32_t)j;
+    chunk_walk(bitmap + e.g0 * 64, j, e.size, minb, maxb, e.s0, roff, rlen, cnt, tot);
 }
 
 // ---- pass C ---------------------------------------------------------------------
@@ -237,20 +346,17 @@ __device__ __forceinline__ u32x4 keep_bytes(u32x4 d, uint32_t n) {
 // (the object starts 16-byte aligned) combined by a byte shift, one when the
 // chunk itself starts aligned.  Loads follow load_piece's rule against the
 // object's length; the chunk's last piece is cut to the chunk's own bytes.
-__global__ __launch_bounds__(256) void k_chunk_fp(const uint8_t *src, uint64_t stride, uint64_t len, uint64_t slots,
-                                                  uint64_t rpo, const uint64_t *roff, const uint32_t *rlen,
-                                                  const uint32_t *cnt, MeasureFp *fp, uint32_t *flen) {
+// Slot `slot` by one wave: its chunk of the len-byte object at ob, or no chunk (live false).
+__device__ __forceinline__ void chunk_fp_slot(const uint8_t *ob, uint64_t len, uint64_t slot, bool live,
+                                              const uint64_t *roff, const uint32_t *rlen, MeasureFp *fp,
+                                              uint32_t *flen) {
     const uint32_t lane = threadIdx.x & 63;
-    const uint64_t slot = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (slot >= slots) return;
-    const uint64_t j = slot / rpo, k = slot - j * rpo;
-    if (k >= cnt[j]) {
+    if (!live) {
         if (lane == 0) flen[slot] = 0;
         return;
     }
     const uint64_t off = roff[slot];
     const uint32_t L = rlen[slot];
-    const uint8_t *ob = src + j * stride;
     const uint32_t sh = (uint32_t)off & 15u;
     const uint64_t base = off - sh;
     const uint32_t np = (L + 15) / 16;
@@ -273,6 +379,28 @@ __global__ __launch_bounds__(256) void k_chunk_fp(const uint8_t *src, uint64_t s
         fp[slot] = fp_final(s0, s1, L);
         flen[slot] = L;
     }
+}
+
+__global__ __launch_bounds__(256) void k_chunk_fp(const uint8_t *src, uint64_t stride, uint64_t len, uint64_t slots,
+                                                  uint64_t rpo, const uint64_t *roff, const uint32_t *rlen,
+                                                  const uint32_t *cnt, MeasureFp *fp, uint32_t *flen) {
+    const uint64_t slot = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (slot >= slots) return;
+    const uint64_t j = slot / rpo, k = slot - j * rpo;
+    chunk_fp_slot(src + j * stride, len, slot, k < cnt[j], roff, rlen, fp, flen);
+}
+
+// The batch form: the slot's entry is the one pass B left in own[]; a slot
+// past its object's count holds no chunk.
+__global__ __launch_bounds__(256) void k_chunk_fp_batch(const uint8_t *src_base, const SpanEnt *ents, uint64_t slots,
+                                                        const uint64_t *roff, const uint32_t *rlen,
+                                                        const uint32_t *cnt, const uint32_t *own, MeasureFp *fp,
+                                                        uint32_t *flen) {
+    const uint64_t slot = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (slot >= slots) return;
+    const uint32_t j = own[slot];
+    const SpanEnt e = ents[j];
+    chunk_fp_slot(src_base + e.off, e.size, slot, slot - e.s0 < cnt[j], roff, rlen, fp, flen);
 }
 
 // ---- distinct count ---------------------------------------------------------------
@@ -381,6 +509,50 @@ hipError_t launch_chunk_fingerprints(const ChunkPlan &P, const uint8_t *src, uin
                        reinterpret_cast<const uint32_t *>(sc + P.len_offset),
                        reinterpret_cast<const uint32_t *>(sc + P.cnt_offset), fp, flen);
     return hipGetLastError();
+}
+
+hipError_t launch_chunk_batch(const ChunkPlan &P, const uint8_t *src_base, const SpanEnt *ents, const SpanTile *tiles,
+                              uint64_t ntiles, uint32_t tshift, uint32_t shift, bool table, uint64_t min_bytes,
+                              uint64_t max_bytes, void *scratch, MeasureFp *fp, uint32_t *flen, uint64_t *tot,
+                              hipEvent_t *tev, hipStream_t s) {
+    (void)hipGetLastError();
+    uint8_t *sc = reinterpret_cast<uint8_t *>(scratch);
+    uint64_t *bitmap = reinterpret_cast<uint64_t *>(sc);
+    uint64_t *roff = reinterpret_cast<uint64_t *>(sc + P.off_offset);
+    uint32_t *rlen = reinterpret_cast<uint32_t *>(sc + P.len_offset);
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(sc + P.cnt_offset);
+    uint32_t *gcnt = reinterpret_cast<uint32_t *>(sc + P.gcnt_offset);
+    uint32_t *own = reinterpret_cast<uint32_t *>(sc + P.own_offset);
+    hipError_t e;
+    if (tev && (e = hipEventRecord(tev[0], s)) != hipSuccess) return e;
+    const uint64_t subs = span_batch_sub_launches(ntiles, tshift);
+    for (uint64_t i = 0; i < subs; ++i) {
+        uint64_t t0, nt;
+        span_batch_sub_launch(ntiles, tshift, i, &t0, &nt);
+        const dim3 g((uint32_t)(nt << tshift));
+        if (table)
+            hipLaunchKernelGGL((k_chunk_candidates_batch<true>), g, dim3(64), 0, s, src_base, tiles, t0, tshift, shift,
+                               bitmap, gcnt);
+        else
+            hipLaunchKernelGGL((k_chunk_candidates_batch<false>), g, dim3(64), 0, s, src_base, tiles, t0, tshift, shift,
+                               bitmap, gcnt);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_chunk_sum, dim3(span_grid_for(P.granules)), dim3(256), 0, s, gcnt, P.granules,
+                       &tot[kChunkTotCandidates]);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (tev && (e = hipEventRecord(tev[1], s)) != hipSuccess) return e;
+    const uint64_t gb = (P.n_objs + 3) / 4, gc = (P.slots + 3) / 4;
+    if (gb > 0x7FFFFFFFull || gc > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_chunk_cuts_batch, dim3((uint32_t)gb), dim3(256), 0, s, bitmap, ents, P.n_objs, min_bytes,
+                       max_bytes, roff, rlen, cnt, own, tot);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (tev && (e = hipEventRecord(tev[2], s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_chunk_fp_batch, dim3((uint32_t)gc), dim3(256), 0, s, src_base, ents, P.slots, roff, rlen, cnt,
+                       own, fp, flen);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (tev && (e = hipEventRecord(tev[3], s)) != hipSuccess) return e;
+    return hipSuccess;
 }
 
 hipError_t launch_chunk_distinct(const MeasureFp *fp, const uint32_t *flen, uint64_t n, void *work, size_t *tmp_bytes,

@@ -69,6 +69,28 @@ int s3dg_lz_add_range(s3dg_lz *h, const void *src, uint64_t obj_size, uint64_t b
     return add_plan(h, P, src, 0, (hipStream_t)stream);
 }
 
+int s3dg_lz_add_batch(s3dg_lz *h, const void *src_base, const s3dg_span *spans, uint64_t n, void *stream) {
+    ACCUM_SCOPE(h, kNullHandle);
+    hipStream_t s = (hipStream_t)stream;
+    SpanBatchCounts C;
+    std::string why;
+    if (!span_batch_check((uint64_t)(uintptr_t)src_base, spans, n, h->block_bytes, 0, &C, &why))
+        return fail(S3DG_EINVAL, why);
+    if (C.live == 0) return S3DG_OK;
+    AccumStream *S = nullptr;
+    if (int r = h->stream_enter(s, &S)) return r;
+    // the entries alone: k_lz_batch walks blocks, not tiles
+    const uint64_t tbytes = span_batch_table_bytes(C.live, 0);
+    void *host = nullptr;
+    if (int r = h->table_stage(*S, tbytes, &host)) return r;
+    span_batch_build(spans, n, h->block_bytes, 0, 0, (SpanEnt *)host, nullptr);
+    if (int r = h->table_upload(*S, tbytes, s)) return r;
+    HIP_TRY(launch_lz_batch((const uint8_t *)src_base, (const SpanEnt *)S->table, C.live, C.blocks, h->block_bytes,
+                            h->cus, h->tot, s),
+            "launch k_lz_batch");
+    return h->stream_mark(*S, s);
+}
+
 int s3dg_lz_get(s3dg_lz *h, s3dg_lz_result *out) {
     if (!out) return fail(S3DG_EINVAL, "null output");
     memset(out, 0, sizeof(*out));

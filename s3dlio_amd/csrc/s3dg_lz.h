@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "s3dg_lz_plan.h"
+#include "s3dg_span_batch_plan.h"
 
 namespace s3dg {
 
@@ -19,5 +20,9 @@ hipError_t lz_kernel_prepare();
 // atomics per wave of the grid (lz_grid).
 hipError_t launch_lz(const LzPlan &P, const uint8_t *src, uint64_t stride, uint64_t block_bytes, int cus,
                      uint64_t *tot, hipStream_t s);
+// The batch form: the add's `blocks` blocks over the `live`
+// entries of its uploaded table, block b of entry j at src_base + off_j + b * block_bytes.
+hipError_t launch_lz_batch(const uint8_t *src_base, const SpanEnt *ents, uint64_t live, uint64_t blocks,
+                           uint64_t block_bytes, int cus, uint64_t *tot, hipStream_t s);
 
 }  // namespace s3dg

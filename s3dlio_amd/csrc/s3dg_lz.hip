@@ -46,8 +46,16 @@ __device__ __forceinline__ void lz_total(uint64_t *tot, int k, uint64_t v) {
 // nothing else.  Every branch around a ballot, a readlane or a barrier is
 // wave-uniform: its condition comes from kernel arguments, ballots and
 // readlanes alone.
-__global__ __launch_bounds__(64) void k_lz(const uint8_t *src, uint64_t stride, uint32_t block_bytes, uint64_t bpo,
-                                           uint32_t last_block, uint64_t blocks, uint64_t *tot) {
+//
+// lz_walk is the body of both kernels.  BATCH false: k_lz's mapping above.
+// BATCH true (k_lz_batch): block bi belongs to the entry
+// found by a wave-uniform binary search over the block prefix of the add's
+// table (at most about 20 scalar steps against at least 64 groups of about
+// 1400 cycles); its start and its length come from the span.
+template <bool BATCH>
+__device__ __forceinline__ void lz_walk(const uint8_t *src, uint64_t stride, uint32_t block_bytes, uint64_t bpo,
+                                        uint32_t last_block, const SpanEnt *ents, uint64_t live, uint64_t blocks,
+                                        uint64_t *tot) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lz_lds[];
     uint32_t *W = lz_lds;
     uint16_t *T = reinterpret_cast<uint16_t *>(lz_lds + block_bytes / 4);
@@ -55,9 +63,18 @@ __global__ __launch_bounds__(64) void k_lz(const uint8_t *src, uint64_t stride, 
     const uint32_t lane = threadIdx.x;
     uint64_t t_bytes = 0, t_blocks = 0, t_lz = 0, t_stored = 0, t_raw = 0, t_matches = 0, t_mbytes = 0, t_lits = 0;
     for (uint64_t bi = blockIdx.x; bi < blocks; bi += gridDim.x) {
-        const uint64_t j = bi / bpo, b = bi - j * bpo;
-        const uint8_t *bs = src + j * stride + b * (uint64_t)block_bytes;
-        const uint32_t n = b + 1 == bpo ? last_block : block_bytes;
+        const uint8_t *bs;
+        uint32_t n;
+        if constexpr (BATCH) {
+            const SpanEnt e = ents[span_batch_find(ents, live, bi)];
+            const uint64_t o = (bi - e.b0) * (uint64_t)block_bytes, rest = e.size - o;
+            bs = src + e.off + o;
+            n = rest < block_bytes ? (uint32_t)rest : block_bytes;
+        } else {
+            const uint64_t j = bi / bpo, b = bi - j * bpo;
+            bs = src + j * stride + b * (uint64_t)block_bytes;
+            n = b + 1 == bpo ? last_block : block_bytes;
+        }
         __syncthreads();   // the previous block is read to its end before LDS is rewritten
         for (uint32_t o = lane * 16; o < n; o += 1024) {
             if (o + 16 <= n) {
@@ -163,10 +180,23 @@ __global__ __launch_bounds__(64) void k_lz(const uint8_t *src, uint64_t stride, 
     }
 }
 
+__global__ __launch_bounds__(64) void k_lz(const uint8_t *src, uint64_t stride, uint32_t block_bytes, uint64_t bpo,
+                                           uint32_t last_block, uint64_t blocks, uint64_t *tot) {
+    lz_walk<false>(src, stride, block_bytes, bpo, last_block, nullptr, 0, blocks, tot);
+}
+
+__global__ __launch_bounds__(64) void k_lz_batch(const uint8_t *src_base, const SpanEnt *ents, uint64_t live,
+                                                 uint32_t block_bytes, uint64_t blocks, uint64_t *tot) {
+    lz_walk<true>(src_base, 0, block_bytes, 0, 0, ents, live, blocks, tot);
+}
+
 }  // namespace
 
 hipError_t lz_kernel_prepare() {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_lz), hipFuncAttributeMaxDynamicSharedMemorySize,
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_lz),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lz_lds_bytes(kLzMaxBlock));
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_lz_batch), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lz_lds_bytes(kLzMaxBlock));
 }
 
@@ -177,6 +207,16 @@ hipError_t launch_lz(const LzPlan &P, const uint8_t *src, uint64_t stride, uint6
     if (grid == 0) return hipSuccess;
     hipLaunchKernelGGL(k_lz, dim3((uint32_t)grid), dim3(64), (size_t)lz_lds_bytes(block_bytes), s, src, stride,
                        (uint32_t)block_bytes, P.bpo, (uint32_t)P.last_block, P.blocks, tot);
+    return hipGetLastError();
+}
+
+hipError_t launch_lz_batch(const uint8_t *src_base, const SpanEnt *ents, uint64_t live, uint64_t blocks,
+                           uint64_t block_bytes, int cus, uint64_t *tot, hipStream_t s) {
+    (void)hipGetLastError();
+    const uint64_t grid = lz_grid(blocks, block_bytes, cus);
+    if (grid == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_lz_batch, dim3((uint32_t)grid), dim3(64), (size_t)lz_lds_bytes(block_bytes), s, src_base, ents,
+                       live, (uint32_t)block_bytes, blocks, tot);
     return hipGetLastError();
 }
 

@@ -67,6 +67,49 @@ int add_plan(s3dg_measure *m, const MeasurePlan &P, const void *src, uint64_t st
     return S3DG_OK;
 }
 
+// One batch add: every span checked, then slots, records and
+// the table reserved on the host, then the table's upload and the passes.
+int add_batch(s3dg_measure *m, const void *src_base, const s3dg_span *spans, uint64_t n, hipStream_t s) {
+    SpanBatchCounts C;
+    std::string why;
+    if (!span_batch_check((uint64_t)(uintptr_t)src_base, spans, n, m->block_bytes, 0, &C, &why))
+        return fail(S3DG_EINVAL, why);
+    if (C.live == 0) return S3DG_OK;
+    if (m->used + C.blocks > kMeasureMaxSlots) return fail(S3DG_EINVAL, "more than 2^40 blocks in one handle");
+    if (int r = fp_reserve(m, m->used + C.blocks)) return r;
+    MeasureStream *Sp = nullptr;
+    if (int r = m->stream_enter(s, &Sp)) return r;
+    MeasureStream &S = *Sp;
+    if (int r = accum_regrow(&S.rec, &S.rec_cap, measure_record_bytes(C.granules), S.ev,
+                             "hipEventSynchronize(measure add)", "hipMalloc(measure records)"))
+        return r;
+    const bool hist = m->flags & S3DG_MEASURE_HIST;
+    if (hist && !S.part) HIP_TRY(hipMalloc(&S.part, measure_hist_part_bytes(m->cus)), "hipMalloc(histogram slots)");
+    const uint32_t tshift = span_batch_tile_shift(C, m->ctx->tile_shift);
+    const uint64_t ntiles = C.ntiles[tshift], tbytes = span_batch_table_bytes(C.live, ntiles);
+    void *host = nullptr;
+    if (int r = m->table_stage(S, tbytes, &host)) return r;
+    span_batch_build(spans, n, m->block_bytes, 0, tshift, (SpanEnt *)host,
+                     (SpanTile *)((uint8_t *)host + span_batch_tile_offset(C.live)));
+    if (int r = m->table_upload(S, tbytes, s)) return r;
+    const SpanEnt *ents = (const SpanEnt *)S.table;
+    const SpanTile *tiles = (const SpanTile *)((const uint8_t *)S.table + span_batch_tile_offset(C.live));
+    const int waves = m->ctx->waves_per_block ? m->ctx->waves_per_block : 1;
+    HIP_TRY(launch_measure_granules_batch((const uint8_t *)src_base, tiles, ntiles, tshift, C.granules,
+                                          (uint32_t)(m->block_bytes / kMeasureGranule), waves, S.rec, s),
+            "launch k_measure_batch");
+    HIP_TRY(launch_measure_blocks_batch(ents, C.live, C.blocks, C.granules, m->block_bytes, S.rec, m->fp + m->used,
+                                        &m->tot[0], s),
+            "launch k_measure_blocks_batch");
+    if (hist)
+        HIP_TRY(launch_byte_hist_batch((const uint8_t *)src_base, tiles, ntiles, tshift, m->cus, S.part, &m->tot[2], s),
+                "launch k_byte_hist_batch");
+    if (int r = m->stream_mark(S, s)) return r;
+    m->used += C.blocks;
+    m->bytes += C.bytes;
+    return S3DG_OK;
+}
+
 void result_clear(s3dg_measure_result *out) { memset(out, 0, sizeof(*out)); }
 
 }  // namespace
@@ -127,6 +170,11 @@ int s3dg_measure_add_range(s3dg_measure *m, const void *src, uint64_t obj_size, 
     if (const char *w = measure_plan_range(&P, (uint64_t)(uintptr_t)src, obj_size, blk_lo, blk_hi, m->block_bytes))
         return fail(S3DG_EINVAL, w);
     return add_plan(m, P, src, 0, (hipStream_t)stream);
+}
+
+int s3dg_measure_add_batch(s3dg_measure *m, const void *src_base, const s3dg_span *spans, uint64_t n, void *stream) {
+    ACCUM_SCOPE(m, kNullHandle);
+    return add_batch(m, src_base, spans, n, (hipStream_t)stream);
 }
 
 int s3dg_measure_get(s3dg_measure *m, s3dg_measure_result *out) {

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "s3dg_measure_plan.h"
+#include "s3dg_span_batch_plan.h"
 
 namespace s3dg {
 
@@ -29,6 +30,19 @@ hipError_t launch_measure_blocks(const MeasurePlan &P, uint64_t block_bytes, con
 uint64_t measure_hist_part_bytes(int cus);
 hipError_t launch_byte_hist(const MeasurePlan &P, const uint8_t *src, uint64_t stride, int cus, void *part,
                             uint64_t *hist, hipStream_t s);
+// The batch forms over an add's uploaded table
+// (s3dg_span_batch_plan.h).  Pass 1: the record of granule g of entry j at
+// index ents[j].g0 + g of rec (measure_record_bytes(granules) bytes), through
+// ntiles tiles of 2^tshift granules; gpb: granules per full block.
+hipError_t launch_measure_granules_batch(const uint8_t *src_base, const SpanTile *tiles, uint64_t ntiles,
+                                         uint32_t tshift, uint64_t granules, uint32_t gpb, int waves, void *rec,
+                                         hipStream_t s);
+// Pass 2: block b of entry j into fp[ents[j].b0 + b].
+hipError_t launch_measure_blocks_batch(const SpanEnt *ents, uint64_t live, uint64_t blocks, uint64_t granules,
+                                       uint64_t block_bytes, const void *rec, MeasureFp *fp, uint64_t *zero_total,
+                                       hipStream_t s);
+hipError_t launch_byte_hist_batch(const uint8_t *src_base, const SpanTile *tiles, uint64_t ntiles, uint32_t tshift,
+                                  int cus, void *part, uint64_t *hist, hipStream_t s);
 // Distinct fingerprints among fp[0, n): two stable radix sorts on a copy in
 // `work` (measure_sort_bytes(n) bytes, then *tmp_bytes of hipCUB scratch), the
 // count added to *distinct (zeroed on the stream first).  work == nullptr:

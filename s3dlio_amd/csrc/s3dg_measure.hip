@@ -78,20 +78,17 @@ __device__ __forceinline__ u32x4 load_ragged(const uint8_t *bs, uint32_t o, uint
 // record).  The reading rules are k_verify_stream's: a 16-byte piece is loaded
 // whole (nontemporal, the bytes are read once) only when it ends at or below
 // the range's length, the ragged piece byte by byte below it, nothing else.
+// One granule by a workgroup of NW waves: bytes [0, L) at bs (L in (0, 4096]),
+// the granule's first piece p0 within its block, its record r.
 template <int NW>
-__global__ __launch_bounds__(64 * NW) void k_measure(const uint8_t *src, uint64_t stride, uint64_t len,
-                                                     uint32_t gran0, uint32_t gpb, uint64_t gpo,
-                                                     uint64_t rec_base, MeasureFp *rfp, uint32_t *rz) {
+__device__ __forceinline__ void measure_granule(const uint8_t *bs, uint32_t L, uint32_t p0, uint64_t r,
+                                                MeasureFp *rfp, uint32_t *rz) {
     constexpr int T = 64 * NW, SPL = 4 / NW;
     __shared__ uint64_t w0[NW], w1[NW];
     __shared__ uint32_t wz[NW];
     const uint32_t t = threadIdx.x;
     const uint32_t lane = t & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const uint32_t g = gran0 + blockIdx.x;
-    const uint8_t *bs = src + (uint64_t)blockIdx.y * stride + (uint64_t)g * kGran;
-    const uint64_t left = len - (uint64_t)g * kGran;              // the launcher keeps g * 4 KiB < len
-    const uint32_t L = left < kGran ? (uint32_t)left : kGran;
     u32x4 G[SPL];
 #pragma unroll
     for (int k = 0; k < SPL; ++k) {
@@ -99,7 +96,6 @@ __global__ __launch_bounds__(64 * NW) void k_measure(const uint8_t *src, uint64_
         G[k] = u32x4{0u, 0u, 0u, 0u};
         if (o + 16 <= L) G[k] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(bs + o));
     }
-    const uint32_t p0 = (g % gpb) * (kGran / 16);                 // the granule's first piece within its block
     uint64_t s0 = 0, s1 = 0;
     uint32_t z = 0;
 #pragma unroll
@@ -121,10 +117,40 @@ __global__ __launch_bounds__(64 * NW) void k_measure(const uint8_t *src, uint64_
         }
     }
     if (t == 0) {
-        const uint64_t r = rec_base + (uint64_t)blockIdx.y * gpo + g;
         rfp[r] = MeasureFp{s0, s1};
         rz[r] = z;
     }
+}
+
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void k_measure(const uint8_t *src, uint64_t stride, uint64_t len,
+                                                     uint32_t gran0, uint32_t gpb, uint64_t gpo,
+                                                     uint64_t rec_base, MeasureFp *rfp, uint32_t *rz) {
+    const uint32_t g = gran0 + blockIdx.x;
+    const uint8_t *bs = src + (uint64_t)blockIdx.y * stride + (uint64_t)g * kGran;
+    const uint64_t left = len - (uint64_t)g * kGran;              // the launcher keeps g * 4 KiB < len
+    const uint32_t L = left < kGran ? (uint32_t)left : kGran;
+    const uint32_t p0 = (g % gpb) * (kGran / 16);                 // the granule's first piece within its block
+    measure_granule<NW>(bs, L, p0, rec_base + (uint64_t)blockIdx.y * gpo + g, rfp, rz);
+}
+
+// The batch form: a 1D grid of slots, slot w = slot
+// w & (2^tshift - 1) of tile tile0 + (w >> tshift).  The tile's record is one
+// wave-uniform 32-byte load in front of the payload loads; a slot past its
+// object's end exits, the whole workgroup alike.
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void k_measure_batch(const uint8_t *src_base, const SpanTile *tiles,
+                                                           uint64_t tile0, uint32_t tshift, uint32_t gpb,
+                                                           MeasureFp *rfp, uint32_t *rz) {
+    const uint32_t w = blockIdx.x;
+    const SpanTile T = tiles[tile0 + (w >> tshift)];
+    const uint32_t k = w & ((1u << tshift) - 1u);
+    const uint64_t o = (uint64_t)k * kGran;
+    if (o >= T.left) return;
+    const uint64_t left = T.left - o;
+    const uint32_t L = left < kGran ? (uint32_t)left : kGran;
+    const uint32_t p0 = ((T.first + k) % gpb) * (kGran / 16);
+    measure_granule<NW>(src_base + T.off + o, L, p0, T.rec + k, rfp, rz);
 }
 
 // ---- pass 2 -------------------------------------------------------------------
@@ -201,6 +227,49 @@ __global__ __launch_bounds__(256) void k_measure_blocks_wave(const MeasureFp *rf
     add_zero_total(z, zero_total);
 }
 
+// The batch forms: block i of the add belongs to the entry found through the
+// block prefix (a search per block: pass 2 moves 36 bytes per block); its
+// length comes from the span.
+__device__ __forceinline__ void block_of_batch(uint64_t i, const SpanEnt *ents, uint64_t live, uint32_t gpb,
+                                               uint64_t block_bytes, uint64_t &r0, uint32_t &ng, uint64_t &blen) {
+    const SpanEnt e = ents[span_batch_find(ents, live, i)];
+    const uint64_t b = i - e.b0, rest = e.size - b * block_bytes;
+    r0 = e.g0 + b * gpb;
+    blen = rest < block_bytes ? rest : block_bytes;
+    ng = (uint32_t)((blen + kGran - 1) / kGran);
+}
+
+// WAVE false: one thread per block; true: one wave per block, four per workgroup.
+template <bool WAVE>
+__global__ __launch_bounds__(256) void k_measure_blocks_batch(const MeasureFp *rfp, const uint32_t *rz,
+                                                              uint64_t nblocks, const SpanEnt *ents, uint64_t live,
+                                                              uint32_t gpb, uint64_t block_bytes, MeasureFp *fp,
+                                                              uint64_t *zero_total) {
+    const uint32_t lane = WAVE ? threadIdx.x & 63 : 0, step = WAVE ? 64 : 1;
+    const uint64_t i = WAVE ? (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6) : (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    uint64_t z = 0;
+    if (i < nblocks) {
+        uint64_t r0, blen, s0 = 0, s1 = 0;
+        uint32_t ng;
+        block_of_batch(i, ents, live, gpb, block_bytes, r0, ng, blen);
+        for (uint32_t k = lane; k < ng; k += step) {
+            const MeasureFp q = rfp[r0 + k];
+            s0 += q.lo;
+            s1 += q.hi;
+            z += rz[r0 + k];
+        }
+        if constexpr (WAVE) {
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                s0 += shfl_xor64(s0, d);
+                s1 += shfl_xor64(s1, d);
+            }
+        }
+        if (lane == 0) fp[i] = fp_final(s0, s1, blen);
+    }
+    add_zero_total(z, zero_total);
+}
+
 // ---- distinct count -------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_fp_split(const MeasureFp *fp, uint64_t n, uint64_t *lo, uint64_t *hi) {
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
@@ -220,6 +289,42 @@ __global__ __launch_bounds__(256) void k_count_distinct(const uint64_t *lo, cons
 }
 
 // ---- byte histogram ---------------------------------------------------------------
+// One granule of the histogram: this thread's 16-byte piece of bytes [0, L) at
+// bs under pass 1's reading rules; zero bytes to z, the others to the wave's counters.
+__device__ __forceinline__ void hist_granule(const uint8_t *bs, uint32_t L, uint32_t *cnt, uint32_t &z) {
+    const uint32_t o = threadIdx.x * 16;
+    if (o + 16 <= L) {
+        const u32x4 d = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(bs + o));
+        const uint32_t dw[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            z += zero_bytes(dw[q]);
+            if (dw[q] == 0) continue;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const uint32_t v = (dw[q] >> (8 * b)) & 0xFFu;
+                if (v) atomicAdd(&cnt[v], 1u);
+            }
+        }
+    } else {
+        for (uint32_t b = 0; o + b < L; ++b) {
+            const uint32_t v = bs[o + b];
+            if (v) atomicAdd(&cnt[v], 1u);
+            else ++z;
+        }
+    }
+}
+
+// The workgroup's counts into its slot of `part`, plain stores.
+__device__ __forceinline__ void hist_flush(uint32_t (*cnt)[256], uint32_t z, uint32_t *part) {
+    const uint32_t t = threadIdx.x, wave = t >> 6;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) z += __shfl_xor(z, d, 64);
+    if ((t & 63) == 0) cnt[wave][0] = z;
+    __syncthreads();
+    part[(uint64_t)blockIdx.x * 256 + t] = cnt[0][t] + cnt[1][t] + cnt[2][t] + cnt[3][t];
+}
+
 // A grid sized to the chip; each workgroup walks granules r = blockIdx.x,
 // + gridDim.x, ... (granule r % gpo of object r / gpo), one 16-byte piece per
 // thread, under pass 1's reading rules.  Zero bytes are counted in registers
@@ -233,38 +338,32 @@ __global__ __launch_bounds__(256) void k_byte_hist(const uint8_t *src, uint64_t 
     for (int w = 0; w < 4; ++w) cnt[w][t] = 0;
     __syncthreads();
     uint32_t z = 0;
-    const uint32_t o = t * 16;
     for (uint64_t r = blockIdx.x; r < total; r += gridDim.x) {
         const uint64_t j = r / gpo, g = r - j * gpo;
-        const uint8_t *bs = src + j * stride + g * kGran;
         const uint64_t left = len - g * kGran;
-        const uint32_t L = left < kGran ? (uint32_t)left : kGran;
-        if (o + 16 <= L) {
-            const u32x4 d = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(bs + o));
-            const uint32_t dw[4] = {d.x, d.y, d.z, d.w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                z += zero_bytes(dw[q]);
-                if (dw[q] == 0) continue;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const uint32_t v = (dw[q] >> (8 * b)) & 0xFFu;
-                    if (v) atomicAdd(&cnt[wave][v], 1u);
-                }
-            }
-        } else {
-            for (uint32_t b = 0; o + b < L; ++b) {
-                const uint32_t v = bs[o + b];
-                if (v) atomicAdd(&cnt[wave][v], 1u);
-                else ++z;
-            }
-        }
+        hist_granule(src + j * stride + g * kGran, left < kGran ? (uint32_t)left : kGran, cnt[wave], z);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) z += __shfl_xor(z, d, 64);
-    if ((t & 63) == 0) cnt[wave][0] = z;
+    hist_flush(cnt, z, part);
+}
+
+// The batch form: the same grid walks the slots of the add's tiles (slot r =
+// slot r & (2^tshift - 1) of tile r >> tshift), skipping those past their
+// object's end.
+__global__ __launch_bounds__(256) void k_byte_hist_batch(const uint8_t *src_base, const SpanTile *tiles,
+                                                         uint64_t total, uint32_t tshift, uint32_t *part) {
+    __shared__ uint32_t cnt[4][256];
+    const uint32_t t = threadIdx.x, wave = t >> 6;
+    for (int w = 0; w < 4; ++w) cnt[w][t] = 0;
     __syncthreads();
-    part[(uint64_t)blockIdx.x * 256 + t] = cnt[0][t] + cnt[1][t] + cnt[2][t] + cnt[3][t];
+    uint32_t z = 0;
+    for (uint64_t r = blockIdx.x; r < total; r += gridDim.x) {
+        const SpanTile T = tiles[r >> tshift];
+        const uint64_t o = (r & ((1ull << tshift) - 1)) * kGran;
+        if (o >= T.left) continue;
+        const uint64_t left = T.left - o;
+        hist_granule(src_base + T.off + o, left < kGran ? (uint32_t)left : kGran, cnt[wave], z);
+    }
+    hist_flush(cnt, z, part);
 }
 
 // hist[b] += the workgroups' counts of value b (one thread per value).
@@ -337,6 +436,62 @@ hipError_t launch_byte_hist(const MeasurePlan &P, const uint8_t *src, uint64_t s
     const uint32_t grid = (uint32_t)(P.records < gmax ? P.records : gmax);
     if (P.records > (uint64_t)grid * kHistMaxGranules) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_byte_hist, dim3(grid), dim3(256), 0, s, src, stride, P.len, P.gpo, P.records,
+                       reinterpret_cast<uint32_t *>(part));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_hist_reduce, dim3(1), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(part), grid, hist);
+    return hipGetLastError();
+}
+
+hipError_t launch_measure_granules_batch(const uint8_t *src_base, const SpanTile *tiles, uint64_t ntiles,
+                                         uint32_t tshift, uint64_t granules, uint32_t gpb, int waves, void *rec,
+                                         hipStream_t s) {
+    (void)hipGetLastError();
+    MeasureFp *rfp = reinterpret_cast<MeasureFp *>(rec);
+    uint32_t *rz = reinterpret_cast<uint32_t *>((uint8_t *)rec + measure_record_zero_offset(granules));
+    const uint64_t subs = span_batch_sub_launches(ntiles, tshift);
+    for (uint64_t i = 0; i < subs; ++i) {
+        uint64_t t0, nt;
+        span_batch_sub_launch(ntiles, tshift, i, &t0, &nt);
+        const dim3 g((uint32_t)(nt << tshift));
+        if (waves == 1)
+            hipLaunchKernelGGL((k_measure_batch<1>), g, dim3(64), 0, s, src_base, tiles, t0, tshift, gpb, rfp, rz);
+        else if (waves == 4)
+            hipLaunchKernelGGL((k_measure_batch<4>), g, dim3(256), 0, s, src_base, tiles, t0, tshift, gpb, rfp, rz);
+        else
+            hipLaunchKernelGGL((k_measure_batch<2>), g, dim3(128), 0, s, src_base, tiles, t0, tshift, gpb, rfp, rz);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_measure_blocks_batch(const SpanEnt *ents, uint64_t live, uint64_t blocks, uint64_t granules,
+                                       uint64_t block_bytes, const void *rec, MeasureFp *fp, uint64_t *zero_total,
+                                       hipStream_t s) {
+    (void)hipGetLastError();
+    const MeasureFp *rfp = reinterpret_cast<const MeasureFp *>(rec);
+    const uint32_t *rz = reinterpret_cast<const uint32_t *>((const uint8_t *)rec + measure_record_zero_offset(granules));
+    const uint32_t gpb = (uint32_t)(block_bytes / kGran);
+    const uint64_t per = gpb < 16 ? 256 : 4;   // blocks per workgroup, as launch_measure_blocks chooses
+    const uint64_t grid = (blocks + per - 1) / per;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (gpb < 16)
+        hipLaunchKernelGGL((k_measure_blocks_batch<false>), dim3((uint32_t)grid), dim3(256), 0, s, rfp, rz, blocks, ents,
+                           live, gpb, block_bytes, fp, zero_total);
+    else
+        hipLaunchKernelGGL((k_measure_blocks_batch<true>), dim3((uint32_t)grid), dim3(256), 0, s, rfp, rz, blocks, ents,
+                           live, gpb, block_bytes, fp, zero_total);
+    return hipGetLastError();
+}
+
+hipError_t launch_byte_hist_batch(const uint8_t *src_base, const SpanTile *tiles, uint64_t ntiles, uint32_t tshift,
+                                  int cus, void *part, uint64_t *hist, hipStream_t s) {
+    (void)hipGetLastError();
+    const uint64_t gmax = hist_grid_max(cus), total = ntiles << tshift;
+    const uint32_t grid = (uint32_t)(total < gmax ? total : gmax);
+    if (total > (uint64_t)grid * kHistMaxGranules) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_byte_hist_batch, dim3(grid), dim3(256), 0, s, src_base, tiles, total, tshift,
                        reinterpret_cast<uint32_t *>(part));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -217,6 +217,32 @@ def _ptr(x) -> int:
     raise TypeError(f"expected a torch CUDA tensor or an int device pointer, got {type(x)}")
 
 
+def _spans(objects):
+    """(s3dg_span array, n, bytes of src the non-empty spans reach) of
+    add_batch's `objects`."""
+    if isinstance(objects, np.ndarray):
+        if objects.dtype != np.uint64 or objects.ndim != 2 or objects.shape[1] != 2:
+            raise ValueError("a span array must be uint64 of shape (n, 2)")
+        a = np.ascontiguousarray(objects)
+    else:
+        rows = [(int(o[0]), int(o[1])) for o in objects]
+        if any(off < 0 or size < 0 or off >= 2**64 or size >= 2**64 for off, size in rows):
+            raise ValueError("span offsets and sizes must fit 64 unsigned bits")
+        a = np.array(rows, dtype=np.uint64).reshape(-1, 2)
+    n = int(a.shape[0])
+    need = 0
+    if n:
+        live = a[:, 1] != 0
+        if live.any():
+            off = a[live, 0]
+            end = off + a[live, 1]   # wraps past 2^64: beyond every tensor
+            need = 2**64 if (end < off).any() else int(end.max())
+    arr = (_lib.Span * max(1, n))()
+    if n:
+        ctypes.memmove(arr, a.ctypes.data, 16 * n)
+    return arr, n, need
+
+
 def _nbytes(x) -> int | None:
     if hasattr(x, "numel") and hasattr(x, "element_size"):
         return int(x.numel() * x.element_size())
@@ -632,6 +658,13 @@ class Context:
             m.add_stream(src, obj_size, n_objs, stride, stream=stream)
             return m.result()
 
+    def measure_batch(self, src, objects, block_bytes: int = 4096, hist: bool = False,
+                      stream=None) -> MeasureResult:
+        """A mixed-size batch as fill_batch lays it out (Measure.add_batch); gaps are never read."""
+        with self.measurer(block_bytes, hist) as m:
+            m.add_batch(src, objects, stream=stream)
+            return m.result()
+
     # -- content-defined chunking (read-only) ------------------------------------
     # How much of a payload is distinct to a store that cuts chunks where a
     # rolling hash over 32 bytes says so, between min_bytes and max_bytes
@@ -658,6 +691,14 @@ class Context:
             h.add_stream(src, obj_size, n_objs, stride, stream=stream)
             return h.result()
 
+    def measure_chunks_batch(self, src, objects, min_bytes: int = CHUNK_DEFAULTS[0],
+                             avg_bytes: int = CHUNK_DEFAULTS[1], max_bytes: int = CHUNK_DEFAULTS[2],
+                             stream=None) -> ChunkResult:
+        """A mixed-size batch as fill_batch lays it out (Chunker.add_batch); gaps are never read."""
+        with self.chunker(min_bytes, avg_bytes, max_bytes) as h:
+            h.add_batch(src, objects, stream=stream)
+            return h.result()
+
     # -- LZ4 compressed size per store block (read-only) ---------------------------
     # The bytes a payload takes in a store that compresses independent blocks
     # of `block_bytes` (a multiple of 4096 up to 65536) with a greedy LZ4
@@ -678,6 +719,12 @@ class Context:
         """n_objs equal objects as fill_stream lays them out; stride gaps are never read."""
         with self.lz_measurer(block_bytes) as m:
             m.add_stream(src, obj_size, n_objs, stride, stream=stream)
+            return m.result()
+
+    def measure_lz_batch(self, src, objects, block_bytes: int = 65536, stream=None) -> LzResult:
+        """A mixed-size batch as fill_batch lays it out (LzMeasure.add_batch); gaps are never read."""
+        with self.lz_measurer(block_bytes) as m:
+            m.add_batch(src, objects, stream=stream)
             return m.result()
 
     def write_ceiling(self, dst, nbytes: int | None = None, pattern: int = 0xA5A5A5A5,
@@ -737,6 +784,17 @@ class _Accum:
         need = (int(n_objs) - 1) * int(stride) + int(obj_size) if n_objs > 0 and obj_size > 0 else 0
         call(f"s3dg_{self._sym}_add_stream", self._h, self._ctx._src(src, need), int(obj_size), int(stride),
              int(n_objs), self._ctx._s(stream))
+
+    def add_batch(self, src, objects, stream=None) -> None:
+        """A mixed-size batch in one asynchronous add: every object measured
+        from its own first byte, the sum of the per-object adds exactly.
+        objects: an iterable whose items start with (off, size), so
+        fill_batch's 5-tuples pass unchanged, or a uint64 numpy array of shape
+        (n, 2).  Spans may come in any order, leave gaps, overlap and repeat;
+        empty ones contribute nothing.  off + size is checked against `src`'s
+        size before any launch (ValueError)."""
+        arr, n, need = _spans(objects)
+        call(f"s3dg_{self._sym}_add_batch", self._h, self._ctx._src(src, need), arr, n, self._ctx._s(stream))
 
     def result(self):
         r = self._rec()
