@@ -6,11 +6,20 @@
 // host slot's staging set.  Private to those three units.
 #pragma once
 #include "s3dg_ctx.h"
-#include "s3dg_span_plan.h"
+#include "s3dg_span_batch_plan.h"
 
 #include <cstring>
 
 namespace s3dg {
+
+// A batch add's uploaded table (s3dg_span_batch_plan.h) on the device: its
+// entries and, for a granule pass, its ntiles tiles of 2^tshift granules.
+struct SpanTable {
+    const SpanEnt *ents;
+    const SpanTile *tiles;
+    uint64_t ntiles;
+    uint32_t tshift;
+};
 
 // What one stream of a handle owns: the event of its latest add.  Adds on one
 // stream are ordered; adds on two streams share nothing but the handle's
@@ -111,12 +120,17 @@ struct Accum {
         return S3DG_OK;
     }
 
-    // A batch add's table on stream s, in two steps.  table_stage: S's pinned
-    // buffer holds `bytes`, idle (a later add on the stream reuses it, so the
-    // earlier upload is waited for), for the caller to build the table in.
-    // table_upload: its copy into S's device buffer, enqueued on s behind the
-    // stream's earlier adds, which read the old table.
-    int table_stage(Stream &S, uint64_t bytes, void **host) {
+    // A batch add's table on stream s, after the caller's span_batch_check
+    // filled C (C.live > 0): built in S's pinned buffer, uploaded to S's device
+    // buffer, *T its parts there.  tiled false: the entries alone.  The pinned
+    // buffer must be idle (a later add on the stream reuses it, so the earlier
+    // upload is waited for); the copy is enqueued on s behind the stream's
+    // earlier adds, which read the old table.
+    int batch_table(Stream &S, const s3dg_span *spans, uint64_t n, const SpanBatchCounts &C, uint64_t block_bytes,
+                    uint64_t min_bytes, bool tiled, hipStream_t s, SpanTable *T) {
+        const uint32_t tshift = tiled ? span_batch_tile_shift(C, ctx->tile_shift) : 0;
+        const uint64_t ntiles = tiled ? C.ntiles[tshift] : 0, toff = span_batch_tile_offset(C.live);
+        const uint64_t bytes = span_batch_table_bytes(C.live, ntiles);
         if (!S.up) HIP_TRY(hipEventCreateWithFlags(&S.up, hipEventDisableTiming), "hipEventCreate");
         else ACCUM_TRY(hipEventSynchronize(S.up), "hipEventSynchronize", " table upload");
         if (bytes > S.stage_cap) {
@@ -127,16 +141,16 @@ struct Accum {
             ACCUM_TRY(hipHostMalloc(&S.stage, cap, hipHostMallocDefault), "hipHostMalloc", " table");
             S.stage_cap = cap;
         }
-        *host = S.stage;
-        return S3DG_OK;
-    }
-    int table_upload(Stream &S, uint64_t bytes, hipStream_t s) {
+        span_batch_build(spans, n, block_bytes, min_bytes, tshift, (SpanEnt *)S.stage,
+                         tiled ? (SpanTile *)((uint8_t *)S.stage + toff) : nullptr);
         // the stream's earlier add may still read the old table
         if (int r = accum_regrow(&S.table, &S.table_cap, span_grow_cap(S.table_cap, bytes), S.ev,
                                  "hipEventSynchronize(add)", "hipMalloc(span table)"))
             return r;
         ACCUM_TRY(hipMemcpyAsync(S.table, S.stage, bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync", " table");
         ACCUM_TRY(hipEventRecord(S.up, s), "hipEventRecord", " table upload");
+        *T = SpanTable{(const SpanEnt *)S.table, tiled ? (const SpanTile *)((const uint8_t *)S.table + toff) : nullptr,
+                       ntiles, tshift};
         return S3DG_OK;
     }
 

@@ -46,7 +46,12 @@ int slots_reserve(s3dg_chunks *h, uint64_t need) {
     return S3DG_OK;
 }
 
-int add_plan(s3dg_chunks *h, const ChunkPlan &P, const void *src, uint64_t stride, hipStream_t s) {
+// One add of plan P on stream s.  C null: the stream form, objects `stride`
+// apart from base on.  Else the batch form of the n checked
+// spans counted in *C, offsets from base: its table is uploaded once the slots
+// and the scratch are reserved.
+int add_plan(s3dg_chunks *h, const ChunkPlan &P, const void *base, uint64_t stride, const s3dg_span *spans, uint64_t n,
+             const SpanBatchCounts *C, hipStream_t s) {
     if (P.n_objs == 0) return S3DG_OK;
     if (h->used + P.slots > kChunkMaxSlots) return fail(S3DG_EINVAL, "more than 2^31 - 1 chunk slots in one handle");
     if (int r = slots_reserve(h, h->used + P.slots)) return r;
@@ -57,23 +62,21 @@ int add_plan(s3dg_chunks *h, const ChunkPlan &P, const void *src, uint64_t strid
     if (int r = accum_regrow(&S.scratch, &S.cap, P.scratch_bytes, S.ev, "hipEventSynchronize(chunks add)",
                              "hipMalloc(chunk scratch)"))
         return r;
+    ChunkSrc src{(const uint8_t *)base, stride, nullptr, nullptr, 0, 0};
+    if (C) {
+        SpanTable T;
+        if (int r = h->batch_table(S, spans, n, *C, 0, h->min_bytes, true, s, &T)) return r;
+        src = ChunkSrc{src.base, 0, T.ents, T.tiles, T.ntiles, T.tshift};
+    }
     const bool timing = h->timing;
     if (timing)
         for (int k = 0; k < 4; ++k)
             if (!S.tev[k]) HIP_TRY(hipEventCreate(&S.tev[k]), "hipEventCreate");
-    if (timing) HIP_TRY(hipEventRecord(S.tev[0], s), "hipEventRecord(chunks pass)");
-    HIP_TRY(launch_chunk_candidates(P, (const uint8_t *)src, stride, 32 - h->bits, h->table, S.scratch, h->tot, s),
-            "launch k_chunk_candidates");
-    if (timing) HIP_TRY(hipEventRecord(S.tev[1], s), "hipEventRecord(chunks pass)");
-    HIP_TRY(launch_chunk_cuts(P, h->min_bytes, h->max_bytes, S.scratch, h->tot, s), "launch k_chunk_cuts");
-    if (timing) HIP_TRY(hipEventRecord(S.tev[2], s), "hipEventRecord(chunks pass)");
-    HIP_TRY(launch_chunk_fingerprints(P, (const uint8_t *)src, stride, S.scratch, h->fp + h->used, h->flen + h->used,
-                                      s),
-            "launch k_chunk_fp");
-    if (timing) {
-        HIP_TRY(hipEventRecord(S.tev[3], s), "hipEventRecord(chunks pass)");
-        h->timed = &S;
-    }
+    const char *step = "";
+    HIP_TRY(launch_chunk_passes(P, src, 32 - h->bits, h->table, h->min_bytes, h->max_bytes, S.scratch,
+                                h->fp + h->used, h->flen + h->used, h->tot, timing ? S.tev : nullptr, &step, s),
+            C ? "launch chunk batch passes" : step);
+    if (timing) h->timed = &S;
     if (int r = h->stream_mark(S, s)) return r;
     h->used += P.slots;
     h->bytes += P.bytes;
@@ -134,49 +137,19 @@ int s3dg_chunks_add_stream(s3dg_chunks *h, const void *src, uint64_t obj_size, u
     ChunkPlan P;
     if (const char *w = chunk_plan_stream(&P, (uint64_t)(uintptr_t)src, obj_size, stride, n_objs, h->min_bytes))
         return fail(S3DG_EINVAL, w);
-    return add_plan(h, P, src, stride, (hipStream_t)stream);
+    return add_plan(h, P, src, stride, nullptr, 0, nullptr, (hipStream_t)stream);
 }
 
 int s3dg_chunks_add_batch(s3dg_chunks *h, const void *src_base, const s3dg_span *spans, uint64_t n, void *stream) {
     ACCUM_SCOPE(h, kNullHandle);
-    hipStream_t s = (hipStream_t)stream;
     SpanBatchCounts C;
     std::string why;
     if (!span_batch_check((uint64_t)(uintptr_t)src_base, spans, n, 0, h->min_bytes, &C, &why))
         return fail(S3DG_EINVAL, why);
     if (C.live == 0) return S3DG_OK;
-    if (h->used + C.slots > kChunkMaxSlots) return fail(S3DG_EINVAL, "more than 2^31 - 1 chunk slots in one handle");
-    if (int r = slots_reserve(h, h->used + C.slots)) return r;
-    ChunkStream *Sp = nullptr;
-    if (int r = h->stream_enter(s, &Sp)) return r;
-    ChunkStream &S = *Sp;
     ChunkPlan P;
     chunk_plan_batch(&P, C.live, C.granules, C.slots, C.bytes);
-    // the stream's earlier add may still use the old scratch
-    if (int r = accum_regrow(&S.scratch, &S.cap, P.scratch_bytes, S.ev, "hipEventSynchronize(chunks add)",
-                             "hipMalloc(chunk scratch)"))
-        return r;
-    const uint32_t tshift = span_batch_tile_shift(C, h->ctx->tile_shift);
-    const uint64_t ntiles = C.ntiles[tshift], tbytes = span_batch_table_bytes(C.live, ntiles);
-    void *host = nullptr;
-    if (int r = h->table_stage(S, tbytes, &host)) return r;
-    span_batch_build(spans, n, 0, h->min_bytes, tshift, (SpanEnt *)host,
-                     (SpanTile *)((uint8_t *)host + span_batch_tile_offset(C.live)));
-    if (int r = h->table_upload(S, tbytes, s)) return r;
-    const bool timing = h->timing;
-    if (timing)
-        for (int k = 0; k < 4; ++k)
-            if (!S.tev[k]) HIP_TRY(hipEventCreate(&S.tev[k]), "hipEventCreate");
-    HIP_TRY(launch_chunk_batch(P, (const uint8_t *)src_base, (const SpanEnt *)S.table,
-                               (const SpanTile *)((const uint8_t *)S.table + span_batch_tile_offset(C.live)), ntiles,
-                               tshift, 32 - h->bits, h->table, h->min_bytes, h->max_bytes, S.scratch, h->fp + h->used,
-                               h->flen + h->used, h->tot, timing ? S.tev : nullptr, s),
-            "launch chunk batch passes");
-    if (timing) h->timed = &S;
-    if (int r = h->stream_mark(S, s)) return r;
-    h->used += C.slots;
-    h->bytes += C.bytes;
-    return S3DG_OK;
+    return add_plan(h, P, src_base, 0, spans, n, &C, (hipStream_t)stream);
 }
 
 int s3dg_chunks_get(s3dg_chunks *h, s3dg_chunk_result *out) {

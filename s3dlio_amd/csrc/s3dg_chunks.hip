@@ -42,91 +42,17 @@ __device__ __forceinline__ void atomic_add64(uint64_t *p, uint64_t v) {
 }
 
 // ---- pass A ---------------------------------------------------------------------
-// blockIdx.x = 4 KiB granule gran0 + x, blockIdx.y = object (src and bitmap
-// already advanced to the sub-launch's first object), one wave per granule,
-// under k_measure's reading rules.  The granule and the 32 bytes before it
-// (the same object's, zeros before its first byte) are staged in LDS as rows
-// of 64 bytes; lane l seeds h over the 31 bytes before its run (row l) and
-// rolls it over the run (row l + 1): h = (h << 1) + G[byte], so after 32 bytes
-// nothing older is left in the 32-bit word.  Positions below 31 of the object
-// and at or above its length are never candidates.  The granule's number of
-// candidates goes to gcnt (summed by k_chunk_sum: an atomic per granule on one
-// word took 12 ns each, 25 ms for 8 GiB).
-template <bool TAB>
-__global__ __launch_bounds__(64) void k_chunk_candidates(const uint8_t *src, uint64_t stride, uint64_t len,
-                                                         uint32_t gran0, uint64_t wpo, uint32_t shift,
-                                                         uint64_t gpo, uint64_t *bitmap, uint32_t *gcnt) {
-    __shared__ uint32_t rows[65 * kRow];
-    __shared__ uint32_t gtab[TAB ? 256 : 1];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t g = gran0 + blockIdx.x;
-    const uint8_t *ob = src + (uint64_t)blockIdx.y * stride;
-    const uint8_t *bs = ob + (uint64_t)g * kGran;
-    const uint64_t left = len - (uint64_t)g * kGran;              // the launcher keeps g * 4 KiB < len
-    const uint32_t L = left < kGran ? (uint32_t)left : kGran;
-    if constexpr (TAB) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) gtab[lane + 64 * k] = gear(lane + 64 * k);
-    }
-    if (lane < 2) {   // row 0, bytes 32..63: the 32 bytes before the granule
-        u32x4 d = u32x4{0u, 0u, 0u, 0u};
-        if (g > 0) d = *reinterpret_cast<const u32x4 *>(bs - 32 + 16 * lane);
-        uint32_t *r = rows + 8 + 4 * lane;
-        r[0] = d.x; r[1] = d.y; r[2] = d.z; r[3] = d.w;
-    }
-    u32x4 D[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t o = (lane + 64 * k) * 16;
-        D[k] = u32x4{0u, 0u, 0u, 0u};
-        if (o + 16 <= L) D[k] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(bs + o));
-        else if (o < L) D[k] = load_piece(bs, o, L);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t q = lane + 64 * k;
-        uint32_t *r = rows + (1 + (q >> 2)) * kRow + (q & 3) * 4;
-        r[0] = D[k].x; r[1] = D[k].y; r[2] = D[k].z; r[3] = D[k].w;
-    }
-    __syncthreads();
-    auto G = [&](uint32_t b) -> uint32_t {
-        if constexpr (TAB) return gtab[b];
-        else return gear(b);
-    };
-    const uint32_t *prev = rows + lane * kRow, *own = prev + kRow;
-    uint32_t h = 0;
-#pragma unroll
-    for (int j = 8; j < 16; ++j) {
-        const uint32_t w = prev[j];
-#pragma unroll
-        for (int b = (j == 8 ? 1 : 0); b < 4; ++b) h = (h << 1) + G((w >> (8 * b)) & 0xFFu);
-    }
-    uint32_t m[2] = {0u, 0u};
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const uint32_t w = own[j];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            h = (h << 1) + G((w >> (8 * b)) & 0xFFu);
-            m[j >> 3] |= (uint32_t)((h >> shift) == 0) << ((4 * j + b) & 31);
-        }
-    }
-    uint64_t bits = (uint64_t)m[0] | ((uint64_t)m[1] << 32);
-    if (g == 0 && lane == 0) bits &= ~0ull << 31;          // a window needs 32 bytes of the object
-    const uint32_t o = lane * 64;
-    if (o >= L) bits = 0;
-    else if (L - o < 64) bits &= ~0ull >> (64 - (L - o));  // nothing at or beyond the object's end
-    bitmap[(uint64_t)blockIdx.y * wpo + (uint64_t)g * 64 + lane] = bits;
-    const uint64_t c = wave_sum64((uint64_t)__builtin_popcountll(bits));
-    if (lane == 0) gcnt[(uint64_t)blockIdx.y * gpo + g] = (uint32_t)c;
-}
-
-// k_chunk_candidates' granule for the batch form (the kernel above keeps its own
-// text: sharing this function changed the register allocation of its <false>
-// instantiation).  One granule by one wave: granule g of its object at bs (nothing before
-// granule 0 is read), `left` > 0 bytes from bs to the object's end; the
-// granule's 64 bitmap words from bitmap[w0] on and its number of candidates to
-// gcnt[gi].
+// One granule by one wave, under k_measure's reading rules: granule g of its
+// object at bs (nothing before granule 0 is read), `left` > 0 bytes from bs to
+// the object's end.  The granule and the 32 bytes before it (the same
+// object's, zeros before its first byte) are staged in LDS as rows of 64
+// bytes; lane l seeds h over the 31 bytes before its run (row l) and rolls it
+// over the run (row l + 1): h = (h << 1) + G[byte], so after 32 bytes nothing
+// older is left in the 32-bit word.  Positions below 31 of the object and at or
+// above its length are never candidates.  The granule's 64 bitmap words go to
+// bitmap[w0] on and its number of candidates to gcnt[gi] (summed by
+// k_chunk_sum: an atomic per granule on one word took 12 ns each, 25 ms for
+// 8 GiB).
 template <bool TAB>
 __device__ __forceinline__ void chunk_granule(const uint8_t *bs, uint32_t g, uint64_t left, uint32_t shift,
                                               uint64_t *bitmap, uint64_t w0, uint32_t *gcnt, uint64_t gi) {
@@ -189,6 +115,19 @@ __device__ __forceinline__ void chunk_granule(const uint8_t *bs, uint32_t g, uin
     bitmap[w0 + lane] = bits;
     const uint64_t c = wave_sum64((uint64_t)__builtin_popcountll(bits));
     if (lane == 0) gcnt[gi] = (uint32_t)c;
+}
+
+// The stream form: blockIdx.x = 4 KiB granule gran0 + x, blockIdx.y = object
+// (src, bitmap and gcnt already advanced to the sub-launch's first object).
+template <bool TAB>
+__global__ __launch_bounds__(64) void k_chunk_candidates(const uint8_t *src, uint64_t stride, uint64_t len,
+                                                         uint32_t gran0, uint64_t wpo, uint32_t shift,
+                                                         uint64_t gpo, uint64_t *bitmap, uint32_t *gcnt) {
+    const uint32_t g = gran0 + blockIdx.x;
+    const uint8_t *bs = src + (uint64_t)blockIdx.y * stride + (uint64_t)g * kGran;
+    const uint64_t left = len - (uint64_t)g * kGran;              // the launcher keeps g * 4 KiB < len
+    chunk_granule<TAB>(bs, g, left, shift, bitmap, (uint64_t)blockIdx.y * wpo + (uint64_t)g * 64, gcnt,
+                       (uint64_t)blockIdx.y * gpo + g);
 }
 
 // The batch form: k_measure_batch's 1D grid of tile slots.
@@ -456,65 +395,9 @@ __global__ __launch_bounds__(256) void k_chunk_count(const MeasureFp *fp, const 
 
 }  // namespace
 
-hipError_t launch_chunk_candidates(const ChunkPlan &P, const uint8_t *src, uint64_t stride, uint32_t shift, bool table,
-                                   void *scratch, uint64_t *tot, hipStream_t s) {
-    (void)hipGetLastError();
-    uint64_t *bitmap = reinterpret_cast<uint64_t *>(scratch);
-    uint32_t *gcnt = reinterpret_cast<uint32_t *>((uint8_t *)scratch + P.gcnt_offset);
-    for (uint64_t iy = 0; iy < P.ny; ++iy) {
-        for (uint64_t ix = 0; ix < P.nx; ++ix) {
-            uint64_t x0, y0;
-            uint32_t gx, gy;
-            chunk_sub_launch(P, ix, iy, &x0, &gx, &y0, &gy);
-            const dim3 g(gx, gy);
-            const uint8_t *p = src + y0 * stride;
-            uint64_t *bm = bitmap + y0 * P.wpo;
-            uint32_t *gc = gcnt + y0 * P.gpo;
-            if (table)
-                hipLaunchKernelGGL((k_chunk_candidates<true>), g, dim3(64), 0, s, p, stride, P.len, (uint32_t)x0, P.wpo,
-                                   shift, P.gpo, bm, gc);
-            else
-                hipLaunchKernelGGL((k_chunk_candidates<false>), g, dim3(64), 0, s, p, stride, P.len, (uint32_t)x0,
-                                   P.wpo, shift, P.gpo, bm, gc);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-    }
-    hipLaunchKernelGGL(k_chunk_sum, dim3(span_grid_for(P.granules)), dim3(256), 0, s, gcnt, P.granules,
-                       &tot[kChunkTotCandidates]);
-    return hipGetLastError();
-}
-
-hipError_t launch_chunk_cuts(const ChunkPlan &P, uint64_t min_bytes, uint64_t max_bytes, void *scratch, uint64_t *tot,
-                             hipStream_t s) {
-    (void)hipGetLastError();
-    uint8_t *sc = reinterpret_cast<uint8_t *>(scratch);
-    const uint64_t grid = (P.n_objs + 3) / 4;
-    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_chunk_cuts, dim3((uint32_t)grid), dim3(256), 0, s, reinterpret_cast<const uint64_t *>(sc),
-                       P.n_objs, P.len, P.wpo, P.rpo, min_bytes, max_bytes,
-                       reinterpret_cast<uint64_t *>(sc + P.off_offset), reinterpret_cast<uint32_t *>(sc + P.len_offset),
-                       reinterpret_cast<uint32_t *>(sc + P.cnt_offset), tot);
-    return hipGetLastError();
-}
-
-hipError_t launch_chunk_fingerprints(const ChunkPlan &P, const uint8_t *src, uint64_t stride, const void *scratch,
-                                     MeasureFp *fp, uint32_t *flen, hipStream_t s) {
-    (void)hipGetLastError();
-    const uint8_t *sc = reinterpret_cast<const uint8_t *>(scratch);
-    const uint64_t grid = (P.slots + 3) / 4;
-    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_chunk_fp, dim3((uint32_t)grid), dim3(256), 0, s, src, stride, P.len, P.slots, P.rpo,
-                       reinterpret_cast<const uint64_t *>(sc + P.off_offset),
-                       reinterpret_cast<const uint32_t *>(sc + P.len_offset),
-                       reinterpret_cast<const uint32_t *>(sc + P.cnt_offset), fp, flen);
-    return hipGetLastError();
-}
-
-hipError_t launch_chunk_batch(const ChunkPlan &P, const uint8_t *src_base, const SpanEnt *ents, const SpanTile *tiles,
-                              uint64_t ntiles, uint32_t tshift, uint32_t shift, bool table, uint64_t min_bytes,
-                              uint64_t max_bytes, void *scratch, MeasureFp *fp, uint32_t *flen, uint64_t *tot,
-                              hipEvent_t *tev, hipStream_t s) {
+hipError_t launch_chunk_passes(const ChunkPlan &P, const ChunkSrc &src, uint32_t shift, bool table,
+                               uint64_t min_bytes, uint64_t max_bytes, void *scratch, MeasureFp *fp, uint32_t *flen,
+                               uint64_t *tot, hipEvent_t *tev, const char **step, hipStream_t s) {
     (void)hipGetLastError();
     uint8_t *sc = reinterpret_cast<uint8_t *>(scratch);
     uint64_t *bitmap = reinterpret_cast<uint64_t *>(sc);
@@ -523,36 +406,64 @@ hipError_t launch_chunk_batch(const ChunkPlan &P, const uint8_t *src_base, const
     uint32_t *cnt = reinterpret_cast<uint32_t *>(sc + P.cnt_offset);
     uint32_t *gcnt = reinterpret_cast<uint32_t *>(sc + P.gcnt_offset);
     uint32_t *own = reinterpret_cast<uint32_t *>(sc + P.own_offset);
+    const bool batch = src.ents != nullptr;
     hipError_t e;
-    if (tev && (e = hipEventRecord(tev[0], s)) != hipSuccess) return e;
-    const uint64_t subs = span_batch_sub_launches(ntiles, tshift);
-    for (uint64_t i = 0; i < subs; ++i) {
-        uint64_t t0, nt;
-        span_batch_sub_launch(ntiles, tshift, i, &t0, &nt);
-        const dim3 g((uint32_t)(nt << tshift));
-        if (table)
-            hipLaunchKernelGGL((k_chunk_candidates_batch<true>), g, dim3(64), 0, s, src_base, tiles, t0, tshift, shift,
-                               bitmap, gcnt);
-        else
-            hipLaunchKernelGGL((k_chunk_candidates_batch<false>), g, dim3(64), 0, s, src_base, tiles, t0, tshift, shift,
-                               bitmap, gcnt);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+    int ev = 0;
+    // the next of tev's events, between two passes
+    auto mark = [&]() -> hipError_t {
+        *step = "hipEventRecord(chunks pass)";
+        return tev ? hipEventRecord(tev[ev++], s) : hipSuccess;
+    };
+    if ((e = mark()) != hipSuccess) return e;
+    *step = "launch k_chunk_candidates";
+    if (batch) {
+        const uint64_t subs = span_batch_sub_launches(src.ntiles, src.tshift);
+        for (uint64_t i = 0; i < subs; ++i) {
+            uint64_t t0, nt;
+            span_batch_sub_launch(src.ntiles, src.tshift, i, &t0, &nt);
+            hipLaunchKernelGGL((table ? k_chunk_candidates_batch<true> : k_chunk_candidates_batch<false>),
+                               dim3((uint32_t)(nt << src.tshift)), dim3(64), 0, s, src.base, src.tiles, t0, src.tshift,
+                               shift, bitmap, gcnt);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+        }
+    } else {
+        for (uint64_t iy = 0; iy < P.ny; ++iy) {
+            for (uint64_t ix = 0; ix < P.nx; ++ix) {
+                uint64_t x0, y0;
+                uint32_t gx, gy;
+                chunk_sub_launch(P, ix, iy, &x0, &gx, &y0, &gy);
+                hipLaunchKernelGGL((table ? k_chunk_candidates<true> : k_chunk_candidates<false>), dim3(gx, gy),
+                                   dim3(64), 0, s, src.base + y0 * src.stride, src.stride, P.len, (uint32_t)x0, P.wpo,
+                                   shift, P.gpo, bitmap + y0 * P.wpo, gcnt + y0 * P.gpo);
+                if ((e = hipGetLastError()) != hipSuccess) return e;
+            }
+        }
     }
     hipLaunchKernelGGL(k_chunk_sum, dim3(span_grid_for(P.granules)), dim3(256), 0, s, gcnt, P.granules,
                        &tot[kChunkTotCandidates]);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (tev && (e = hipEventRecord(tev[1], s)) != hipSuccess) return e;
+    if ((e = mark()) != hipSuccess) return e;
+    *step = "launch k_chunk_cuts";
     const uint64_t gb = (P.n_objs + 3) / 4, gc = (P.slots + 3) / 4;
-    if (gb > 0x7FFFFFFFull || gc > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_chunk_cuts_batch, dim3((uint32_t)gb), dim3(256), 0, s, bitmap, ents, P.n_objs, min_bytes,
-                       max_bytes, roff, rlen, cnt, own, tot);
+    if (gb > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (batch)
+        hipLaunchKernelGGL(k_chunk_cuts_batch, dim3((uint32_t)gb), dim3(256), 0, s, bitmap, src.ents, P.n_objs,
+                           min_bytes, max_bytes, roff, rlen, cnt, own, tot);
+    else
+        hipLaunchKernelGGL(k_chunk_cuts, dim3((uint32_t)gb), dim3(256), 0, s, bitmap, P.n_objs, P.len, P.wpo, P.rpo,
+                           min_bytes, max_bytes, roff, rlen, cnt, tot);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (tev && (e = hipEventRecord(tev[2], s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_chunk_fp_batch, dim3((uint32_t)gc), dim3(256), 0, s, src_base, ents, P.slots, roff, rlen, cnt,
-                       own, fp, flen);
+    if ((e = mark()) != hipSuccess) return e;
+    *step = "launch k_chunk_fp";
+    if (gc > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (batch)
+        hipLaunchKernelGGL(k_chunk_fp_batch, dim3((uint32_t)gc), dim3(256), 0, s, src.base, src.ents, P.slots, roff,
+                           rlen, cnt, own, fp, flen);
+    else
+        hipLaunchKernelGGL(k_chunk_fp, dim3((uint32_t)gc), dim3(256), 0, s, src.base, src.stride, P.len, P.slots, P.rpo,
+                           roff, rlen, cnt, fp, flen);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (tev && (e = hipEventRecord(tev[3], s)) != hipSuccess) return e;
-    return hipSuccess;
+    return mark();
 }
 
 hipError_t launch_chunk_distinct(const MeasureFp *fp, const uint32_t *flen, uint64_t n, void *work, size_t *tmp_bytes,

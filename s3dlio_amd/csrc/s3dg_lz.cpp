@@ -80,13 +80,9 @@ int s3dg_lz_add_batch(s3dg_lz *h, const void *src_base, const s3dg_span *spans, 
     AccumStream *S = nullptr;
     if (int r = h->stream_enter(s, &S)) return r;
     // the entries alone: k_lz_batch walks blocks, not tiles
-    const uint64_t tbytes = span_batch_table_bytes(C.live, 0);
-    void *host = nullptr;
-    if (int r = h->table_stage(*S, tbytes, &host)) return r;
-    span_batch_build(spans, n, h->block_bytes, 0, 0, (SpanEnt *)host, nullptr);
-    if (int r = h->table_upload(*S, tbytes, s)) return r;
-    HIP_TRY(launch_lz_batch((const uint8_t *)src_base, (const SpanEnt *)S->table, C.live, C.blocks, h->block_bytes,
-                            h->cus, h->tot, s),
+    SpanTable T;
+    if (int r = h->batch_table(*S, spans, n, C, h->block_bytes, 0, false, s, &T)) return r;
+    HIP_TRY(launch_lz_batch((const uint8_t *)src_base, T.ents, C.live, C.blocks, h->block_bytes, h->cus, h->tot, s),
             "launch k_lz_batch");
     return h->stream_mark(*S, s);
 }

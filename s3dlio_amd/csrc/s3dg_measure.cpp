@@ -40,74 +40,68 @@ int fp_reserve(s3dg_measure *m, uint64_t need) {
     return S3DG_OK;
 }
 
-int add_plan(s3dg_measure *m, const MeasurePlan &P, const void *src, uint64_t stride, hipStream_t s) {
-    if (P.n_objs == 0) return S3DG_OK;
-    if (m->used + P.slots > kMeasureMaxSlots) return fail(S3DG_EINVAL, "more than 2^40 blocks in one handle");
-    if (int r = fp_reserve(m, m->used + P.slots)) return r;
+// What a stream add and a batch add share around their launches: room for
+// `slots` more fingerprints, stream s's state with the records of `records`
+// granules and, for a histogram, its slots; then launch(S, waves, hist)
+// enqueues the passes, and the add becomes the stream's latest.
+template <class Launch>
+int add_on_stream(s3dg_measure *m, uint64_t slots, uint64_t records, uint64_t bytes, hipStream_t s, Launch launch) {
+    if (m->used + slots > kMeasureMaxSlots) return fail(S3DG_EINVAL, "more than 2^40 blocks in one handle");
+    if (int r = fp_reserve(m, m->used + slots)) return r;
     MeasureStream *Sp = nullptr;
     if (int r = m->stream_enter(s, &Sp)) return r;
     MeasureStream &S = *Sp;
     // the stream's earlier add may still read the old records
-    if (int r = accum_regrow(&S.rec, &S.rec_cap, measure_record_bytes(P.records), S.ev,
+    if (int r = accum_regrow(&S.rec, &S.rec_cap, measure_record_bytes(records), S.ev,
                              "hipEventSynchronize(measure add)", "hipMalloc(measure records)"))
         return r;
     const bool hist = m->flags & S3DG_MEASURE_HIST;
     if (hist && !S.part) HIP_TRY(hipMalloc(&S.part, measure_hist_part_bytes(m->cus)), "hipMalloc(histogram slots)");
     // waves per granule: the context's knob; auto = 1 (the fewest cross-wave sums, measured fastest)
     const int waves = m->ctx->waves_per_block ? m->ctx->waves_per_block : 1;
-    HIP_TRY(launch_measure_granules(P, (const uint8_t *)src, stride, waves, S.rec, s), "launch k_measure");
-    HIP_TRY(launch_measure_blocks(P, m->block_bytes, S.rec, m->fp + m->used, &m->tot[0], s),
-            "launch k_measure_blocks");
-    if (hist)
-        HIP_TRY(launch_byte_hist(P, (const uint8_t *)src, stride, m->cus, S.part, &m->tot[2], s),
-                "launch k_byte_hist");
+    if (int r = launch(S, waves, hist)) return r;
     if (int r = m->stream_mark(S, s)) return r;
-    m->used += P.slots;
-    m->bytes += P.bytes;
+    m->used += slots;
+    m->bytes += bytes;
     return S3DG_OK;
 }
 
-// One batch add: every span checked, then slots, records and
-// the table reserved on the host, then the table's upload and the passes.
+int add_plan(s3dg_measure *m, const MeasurePlan &P, const void *src, uint64_t stride, hipStream_t s) {
+    if (P.n_objs == 0) return S3DG_OK;
+    return add_on_stream(m, P.slots, P.records, P.bytes, s, [&](MeasureStream &S, int waves, bool hist) -> int {
+        HIP_TRY(launch_measure_granules(P, (const uint8_t *)src, stride, waves, S.rec, s), "launch k_measure");
+        HIP_TRY(launch_measure_blocks(P, m->block_bytes, S.rec, m->fp + m->used, &m->tot[0], s),
+                "launch k_measure_blocks");
+        if (hist)
+            HIP_TRY(launch_byte_hist(P, (const uint8_t *)src, stride, m->cus, S.part, &m->tot[2], s),
+                    "launch k_byte_hist");
+        return S3DG_OK;
+    });
+}
+
+// One batch add: every span checked, then slots and records
+// reserved on the host, then the table's upload and the passes.
 int add_batch(s3dg_measure *m, const void *src_base, const s3dg_span *spans, uint64_t n, hipStream_t s) {
     SpanBatchCounts C;
     std::string why;
     if (!span_batch_check((uint64_t)(uintptr_t)src_base, spans, n, m->block_bytes, 0, &C, &why))
         return fail(S3DG_EINVAL, why);
     if (C.live == 0) return S3DG_OK;
-    if (m->used + C.blocks > kMeasureMaxSlots) return fail(S3DG_EINVAL, "more than 2^40 blocks in one handle");
-    if (int r = fp_reserve(m, m->used + C.blocks)) return r;
-    MeasureStream *Sp = nullptr;
-    if (int r = m->stream_enter(s, &Sp)) return r;
-    MeasureStream &S = *Sp;
-    if (int r = accum_regrow(&S.rec, &S.rec_cap, measure_record_bytes(C.granules), S.ev,
-                             "hipEventSynchronize(measure add)", "hipMalloc(measure records)"))
-        return r;
-    const bool hist = m->flags & S3DG_MEASURE_HIST;
-    if (hist && !S.part) HIP_TRY(hipMalloc(&S.part, measure_hist_part_bytes(m->cus)), "hipMalloc(histogram slots)");
-    const uint32_t tshift = span_batch_tile_shift(C, m->ctx->tile_shift);
-    const uint64_t ntiles = C.ntiles[tshift], tbytes = span_batch_table_bytes(C.live, ntiles);
-    void *host = nullptr;
-    if (int r = m->table_stage(S, tbytes, &host)) return r;
-    span_batch_build(spans, n, m->block_bytes, 0, tshift, (SpanEnt *)host,
-                     (SpanTile *)((uint8_t *)host + span_batch_tile_offset(C.live)));
-    if (int r = m->table_upload(S, tbytes, s)) return r;
-    const SpanEnt *ents = (const SpanEnt *)S.table;
-    const SpanTile *tiles = (const SpanTile *)((const uint8_t *)S.table + span_batch_tile_offset(C.live));
-    const int waves = m->ctx->waves_per_block ? m->ctx->waves_per_block : 1;
-    HIP_TRY(launch_measure_granules_batch((const uint8_t *)src_base, tiles, ntiles, tshift, C.granules,
-                                          (uint32_t)(m->block_bytes / kMeasureGranule), waves, S.rec, s),
-            "launch k_measure_batch");
-    HIP_TRY(launch_measure_blocks_batch(ents, C.live, C.blocks, C.granules, m->block_bytes, S.rec, m->fp + m->used,
-                                        &m->tot[0], s),
-            "launch k_measure_blocks_batch");
-    if (hist)
-        HIP_TRY(launch_byte_hist_batch((const uint8_t *)src_base, tiles, ntiles, tshift, m->cus, S.part, &m->tot[2], s),
-                "launch k_byte_hist_batch");
-    if (int r = m->stream_mark(S, s)) return r;
-    m->used += C.blocks;
-    m->bytes += C.bytes;
-    return S3DG_OK;
+    return add_on_stream(m, C.blocks, C.granules, C.bytes, s, [&](MeasureStream &S, int waves, bool hist) -> int {
+        SpanTable T;
+        if (int r = m->batch_table(S, spans, n, C, m->block_bytes, 0, true, s, &T)) return r;
+        HIP_TRY(launch_measure_granules_batch((const uint8_t *)src_base, T.tiles, T.ntiles, T.tshift, C.granules,
+                                              (uint32_t)(m->block_bytes / kMeasureGranule), waves, S.rec, s),
+                "launch k_measure_batch");
+        HIP_TRY(launch_measure_blocks_batch(T.ents, C.live, C.blocks, C.granules, m->block_bytes, S.rec,
+                                            m->fp + m->used, &m->tot[0], s),
+                "launch k_measure_blocks_batch");
+        if (hist)
+            HIP_TRY(launch_byte_hist_batch((const uint8_t *)src_base, T.tiles, T.ntiles, T.tshift, m->cus, S.part,
+                                           &m->tot[2], s),
+                    "launch k_byte_hist_batch");
+        return S3DG_OK;
+    });
 }
 
 void result_clear(s3dg_measure_result *out) { memset(out, 0, sizeof(*out)); }

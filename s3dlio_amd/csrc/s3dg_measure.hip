@@ -168,104 +168,69 @@ __device__ __forceinline__ void add_zero_total(uint64_t z, uint64_t *total) {
     }
 }
 
-// Block i of the add (object i / bpo, its block i % bpo): first record, granules, byte length.
-__device__ __forceinline__ void block_of(uint64_t i, uint64_t bpo, uint64_t gpo, uint32_t gpb, uint64_t block_bytes,
-                                         uint64_t last_block, uint64_t &r0, uint32_t &ng, uint64_t &blen) {
-    const uint64_t j = i / bpo, b = i - j * bpo;
-    r0 = j * gpo + b * gpb;
-    blen = b + 1 == bpo ? last_block : block_bytes;
-    ng = (uint32_t)((blen + kGran - 1) / kGran);
-}
-
-// One thread per block (blocks of a few granules).
-__global__ __launch_bounds__(256) void k_measure_blocks(const MeasureFp *rfp, const uint32_t *rz, uint64_t nblocks,
-                                                        uint64_t bpo, uint64_t gpo, uint32_t gpb,
-                                                        uint64_t block_bytes, uint64_t last_block, MeasureFp *fp,
-                                                        uint64_t *zero_total) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    uint64_t z = 0;
-    if (i < nblocks) {
-        uint64_t r0, blen, s0 = 0, s1 = 0;
-        uint32_t ng;
-        block_of(i, bpo, gpo, gpb, block_bytes, last_block, r0, ng, blen);
-        for (uint32_t k = 0; k < ng; ++k) {
-            const MeasureFp q = rfp[r0 + k];
-            s0 += q.lo;
-            s1 += q.hi;
-            z += rz[r0 + k];
-        }
-        fp[i] = fp_final(s0, s1, blen);
+// One block's records rfp / rz [r0, r0 + ng) summed and finalised into *out
+// (blen: the block's bytes).  WAVE false: by the calling thread; true: by the
+// 64 lanes of its wave.  Returns the thread's share of the block's zero bytes.
+template <bool WAVE>
+__device__ __forceinline__ uint64_t block_sum(const MeasureFp *rfp, const uint32_t *rz, uint64_t r0, uint32_t ng,
+                                              uint64_t blen, MeasureFp *out) {
+    const uint32_t lane = WAVE ? threadIdx.x & 63 : 0, step = WAVE ? 64 : 1;
+    uint64_t s0 = 0, s1 = 0, z = 0;
+    for (uint32_t k = lane; k < ng; k += step) {
+        const MeasureFp q = rfp[r0 + k];
+        s0 += q.lo;
+        s1 += q.hi;
+        z += rz[r0 + k];
     }
-    add_zero_total(z, zero_total);
-}
-
-// One wave per block (blocks of many granules), four blocks per workgroup.
-__global__ __launch_bounds__(256) void k_measure_blocks_wave(const MeasureFp *rfp, const uint32_t *rz,
-                                                             uint64_t nblocks, uint64_t bpo, uint64_t gpo,
-                                                             uint32_t gpb, uint64_t block_bytes, uint64_t last_block,
-                                                             MeasureFp *fp, uint64_t *zero_total) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    uint64_t z = 0;
-    if (i < nblocks) {
-        uint64_t r0, blen, s0 = 0, s1 = 0;
-        uint32_t ng;
-        block_of(i, bpo, gpo, gpb, block_bytes, last_block, r0, ng, blen);
-        for (uint32_t k = lane; k < ng; k += 64) {
-            const MeasureFp q = rfp[r0 + k];
-            s0 += q.lo;
-            s1 += q.hi;
-            z += rz[r0 + k];
-        }
+    if constexpr (WAVE) {
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) {
             s0 += shfl_xor64(s0, d);
             s1 += shfl_xor64(s1, d);
         }
-        if (lane == 0) fp[i] = fp_final(s0, s1, blen);
+    }
+    if (lane == 0) *out = fp_final(s0, s1, blen);
+    return z;
+}
+
+// The block a thread works on.  WAVE false: one thread per block (blocks of a
+// few granules); true: one wave per block (blocks of many), four per workgroup.
+template <bool WAVE>
+__device__ __forceinline__ uint64_t block_index() {
+    return WAVE ? (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6) : (uint64_t)blockIdx.x * 256 + threadIdx.x;
+}
+
+// The stream form: block i of the add is block i % bpo of object i / bpo.
+template <bool WAVE>
+__global__ __launch_bounds__(256) void k_measure_blocks(const MeasureFp *rfp, const uint32_t *rz, uint64_t nblocks,
+                                                        uint64_t bpo, uint64_t gpo, uint32_t gpb,
+                                                        uint64_t block_bytes, uint64_t last_block, MeasureFp *fp,
+                                                        uint64_t *zero_total) {
+    const uint64_t i = block_index<WAVE>();
+    uint64_t z = 0;
+    if (i < nblocks) {
+        const uint64_t j = i / bpo, b = i - j * bpo;
+        const uint64_t blen = b + 1 == bpo ? last_block : block_bytes;
+        z = block_sum<WAVE>(rfp, rz, j * gpo + b * gpb, (uint32_t)((blen + kGran - 1) / kGran), blen, &fp[i]);
     }
     add_zero_total(z, zero_total);
 }
 
-// The batch forms: block i of the add belongs to the entry found through the
+// The batch form: block i of the add belongs to the entry found through the
 // block prefix (a search per block: pass 2 moves 36 bytes per block); its
 // length comes from the span.
-__device__ __forceinline__ void block_of_batch(uint64_t i, const SpanEnt *ents, uint64_t live, uint32_t gpb,
-                                               uint64_t block_bytes, uint64_t &r0, uint32_t &ng, uint64_t &blen) {
-    const SpanEnt e = ents[span_batch_find(ents, live, i)];
-    const uint64_t b = i - e.b0, rest = e.size - b * block_bytes;
-    r0 = e.g0 + b * gpb;
-    blen = rest < block_bytes ? rest : block_bytes;
-    ng = (uint32_t)((blen + kGran - 1) / kGran);
-}
-
-// WAVE false: one thread per block; true: one wave per block, four per workgroup.
 template <bool WAVE>
 __global__ __launch_bounds__(256) void k_measure_blocks_batch(const MeasureFp *rfp, const uint32_t *rz,
                                                               uint64_t nblocks, const SpanEnt *ents, uint64_t live,
                                                               uint32_t gpb, uint64_t block_bytes, MeasureFp *fp,
                                                               uint64_t *zero_total) {
-    const uint32_t lane = WAVE ? threadIdx.x & 63 : 0, step = WAVE ? 64 : 1;
-    const uint64_t i = WAVE ? (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6) : (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t i = block_index<WAVE>();
     uint64_t z = 0;
     if (i < nblocks) {
-        uint64_t r0, blen, s0 = 0, s1 = 0;
-        uint32_t ng;
-        block_of_batch(i, ents, live, gpb, block_bytes, r0, ng, blen);
-        for (uint32_t k = lane; k < ng; k += step) {
-            const MeasureFp q = rfp[r0 + k];
-            s0 += q.lo;
-            s1 += q.hi;
-            z += rz[r0 + k];
-        }
-        if constexpr (WAVE) {
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                s0 += shfl_xor64(s0, d);
-                s1 += shfl_xor64(s1, d);
-            }
-        }
-        if (lane == 0) fp[i] = fp_final(s0, s1, blen);
+        const SpanEnt e = ents[span_batch_find(ents, live, i)];
+        const uint64_t b = i - e.b0, rest = e.size - b * block_bytes;
+        const uint64_t blen = rest < block_bytes ? rest : block_bytes;
+        z = block_sum<WAVE>(rfp, rz, e.g0 + b * gpb, (uint32_t)((blen + kGran - 1) / kGran), blen, &fp[i]);
     }
     add_zero_total(z, zero_total);
 }
@@ -325,45 +290,53 @@ __device__ __forceinline__ void hist_flush(uint32_t (*cnt)[256], uint32_t z, uin
     part[(uint64_t)blockIdx.x * 256 + t] = cnt[0][t] + cnt[1][t] + cnt[2][t] + cnt[3][t];
 }
 
-// A grid sized to the chip; each workgroup walks granules r = blockIdx.x,
-// + gridDim.x, ... (granule r % gpo of object r / gpo), one 16-byte piece per
-// thread, under pass 1's reading rules.  Zero bytes are counted in registers
-// (half of a compress-2 payload: every lane would meet on one LDS word); the
-// other values go to the wave's own 256 LDS counters.  One flush per workgroup
-// into its slot of `part`, plain stores.
-__global__ __launch_bounds__(256) void k_byte_hist(const uint8_t *src, uint64_t stride, uint64_t len, uint64_t gpo,
-                                                   uint64_t total, uint32_t *part) {
+// A grid sized to the chip; each workgroup walks slots r = blockIdx.x,
+// + gridDim.x, ... below `total`, one 16-byte piece per thread, under pass 1's
+// reading rules.  locate(r, bs, L): slot r's granule is bytes [0, L) at bs, or
+// false: it has none.  Zero bytes are counted in registers (half of a
+// compress-2 payload: every lane would meet on one LDS word); the other values
+// go to the wave's own 256 LDS counters.  One flush per workgroup into its
+// slot of `part`, plain stores.
+template <class Locate>
+__device__ __forceinline__ void hist_walk(uint64_t total, uint32_t *part, Locate locate) {
     __shared__ uint32_t cnt[4][256];
     const uint32_t t = threadIdx.x, wave = t >> 6;
     for (int w = 0; w < 4; ++w) cnt[w][t] = 0;
     __syncthreads();
     uint32_t z = 0;
     for (uint64_t r = blockIdx.x; r < total; r += gridDim.x) {
-        const uint64_t j = r / gpo, g = r - j * gpo;
-        const uint64_t left = len - g * kGran;
-        hist_granule(src + j * stride + g * kGran, left < kGran ? (uint32_t)left : kGran, cnt[wave], z);
+        const uint8_t *bs;
+        uint32_t L;
+        if (locate(r, bs, L)) hist_granule(bs, L, cnt[wave], z);
     }
     hist_flush(cnt, z, part);
 }
 
-// The batch form: the same grid walks the slots of the add's tiles (slot r =
-// slot r & (2^tshift - 1) of tile r >> tshift), skipping those past their
-// object's end.
+// The stream form: slot r is granule r % gpo of object r / gpo.
+__global__ __launch_bounds__(256) void k_byte_hist(const uint8_t *src, uint64_t stride, uint64_t len, uint64_t gpo,
+                                                   uint64_t total, uint32_t *part) {
+    hist_walk(total, part, [&](uint64_t r, const uint8_t *&bs, uint32_t &L) {
+        const uint64_t j = r / gpo, g = r - j * gpo;
+        const uint64_t left = len - g * kGran;
+        bs = src + j * stride + g * kGran;
+        L = left < kGran ? (uint32_t)left : kGran;
+        return true;
+    });
+}
+
+// The batch form: slot r is slot r & (2^tshift - 1) of the add's tile
+// r >> tshift; those past their object's end are skipped.
 __global__ __launch_bounds__(256) void k_byte_hist_batch(const uint8_t *src_base, const SpanTile *tiles,
                                                          uint64_t total, uint32_t tshift, uint32_t *part) {
-    __shared__ uint32_t cnt[4][256];
-    const uint32_t t = threadIdx.x, wave = t >> 6;
-    for (int w = 0; w < 4; ++w) cnt[w][t] = 0;
-    __syncthreads();
-    uint32_t z = 0;
-    for (uint64_t r = blockIdx.x; r < total; r += gridDim.x) {
+    hist_walk(total, part, [&](uint64_t r, const uint8_t *&bs, uint32_t &L) {
         const SpanTile T = tiles[r >> tshift];
         const uint64_t o = (r & ((1ull << tshift) - 1)) * kGran;
-        if (o >= T.left) continue;
+        if (o >= T.left) return false;
         const uint64_t left = T.left - o;
-        hist_granule(src_base + T.off + o, left < kGran ? (uint32_t)left : kGran, cnt[wave], z);
-    }
-    hist_flush(cnt, z, part);
+        bs = src_base + T.off + o;
+        L = left < kGran ? (uint32_t)left : kGran;
+        return true;
+    });
 }
 
 // hist[b] += the workgroups' counts of value b (one thread per value).
@@ -379,30 +352,60 @@ __global__ __launch_bounds__(256) void k_hist_reduce(const uint32_t *part, uint3
 constexpr uint64_t kHistMaxGranules = 1ull << 19;
 uint32_t hist_grid_max(int cus) { return (uint32_t)(cus > 0 ? cus : 256) * 8; }
 
+// The histogram of an add of `total` slots: walk(grid, part) launches its walk
+// on a grid sized to the chip, then the workgroups' counts are added to hist.
+template <class Walk>
+hipError_t hist_launch(uint64_t total, int cus, void *part, uint64_t *hist, hipStream_t s, Walk walk) {
+    (void)hipGetLastError();
+    const uint64_t gmax = hist_grid_max(cus);
+    const uint32_t grid = (uint32_t)(total < gmax ? total : gmax);
+    if (total > (uint64_t)grid * kHistMaxGranules) return hipErrorInvalidValue;
+    walk(dim3(grid), reinterpret_cast<uint32_t *>(part));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_hist_reduce, dim3(1), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(part), grid, hist);
+    return hipGetLastError();
+}
+
+// Pass 1's instantiation of kernel template K for `waves` wave64s per granule
+// (1 or 4; anything else: 2) and its workgroup.
+#define MEASURE_FOR_WAVES(K, waves) ((waves) == 1 ? K<1> : (waves) == 4 ? K<4> : K<2>)
+dim3 waves_block(int waves) { return dim3(waves == 1 ? 64 : waves == 4 ? 256 : 128); }
+
+// Pass 2 over `blocks` blocks of gpb granules: one thread per block (256 per
+// workgroup) for blocks below kMeasureWaveBlocksFrom granules, one wave per
+// block (4 per workgroup) from there on.  launch(wave, grid) enqueues it.
+constexpr uint32_t kMeasureWaveBlocksFrom = 16;
+template <class Launch>
+hipError_t blocks_launch(uint64_t blocks, uint32_t gpb, Launch launch) {
+    (void)hipGetLastError();
+    const bool wave = gpb >= kMeasureWaveBlocksFrom;
+    const uint64_t per = wave ? 4 : 256;   // blocks per workgroup
+    const uint64_t grid = (blocks + per - 1) / per;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    launch(wave, dim3((uint32_t)grid));
+    return hipGetLastError();
+}
+
+// Pass 1's records in rec: the partial fingerprints, then the zero counts of n granules.
+uint32_t *record_zeros(const void *rec, uint64_t n) {
+    return reinterpret_cast<uint32_t *>((uint8_t *)rec + measure_record_zero_offset(n));
+}
+
 }  // namespace
 
 hipError_t launch_measure_granules(const MeasurePlan &P, const uint8_t *src, uint64_t stride, int waves, void *rec,
                                    hipStream_t s) {
     (void)hipGetLastError();
     MeasureFp *rfp = reinterpret_cast<MeasureFp *>(rec);
-    uint32_t *rz = reinterpret_cast<uint32_t *>((uint8_t *)rec + measure_record_zero_offset(P.records));
+    uint32_t *rz = record_zeros(rec, P.records);
     for (uint64_t iy = 0; iy < P.ny; ++iy) {
         for (uint64_t ix = 0; ix < P.nx; ++ix) {
             uint64_t x0, y0;
             uint32_t gx, gy;
             measure_sub_launch(P, ix, iy, &x0, &gx, &y0, &gy);
-            const dim3 g(gx, gy);
-            const uint8_t *p = src + y0 * stride;
-            const uint64_t rb = y0 * P.gpo;
-            if (waves == 1)
-                hipLaunchKernelGGL((k_measure<1>), g, dim3(64), 0, s, p, stride, P.len, (uint32_t)x0, P.gpb, P.gpo, rb,
-                                   rfp, rz);
-            else if (waves == 4)
-                hipLaunchKernelGGL((k_measure<4>), g, dim3(256), 0, s, p, stride, P.len, (uint32_t)x0, P.gpb, P.gpo,
-                                   rb, rfp, rz);
-            else
-                hipLaunchKernelGGL((k_measure<2>), g, dim3(128), 0, s, p, stride, P.len, (uint32_t)x0, P.gpb, P.gpo,
-                                   rb, rfp, rz);
+            hipLaunchKernelGGL(MEASURE_FOR_WAVES(k_measure, waves), dim3(gx, gy), waves_block(waves), 0, s,
+                               src + y0 * stride, stride, P.len, (uint32_t)x0, P.gpb, P.gpo, y0 * P.gpo, rfp, rz);
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
         }
@@ -412,35 +415,21 @@ hipError_t launch_measure_granules(const MeasurePlan &P, const uint8_t *src, uin
 
 hipError_t launch_measure_blocks(const MeasurePlan &P, uint64_t block_bytes, const void *rec, MeasureFp *fp,
                                  uint64_t *zero_total, hipStream_t s) {
-    (void)hipGetLastError();
     const MeasureFp *rfp = reinterpret_cast<const MeasureFp *>(rec);
-    const uint32_t *rz = reinterpret_cast<const uint32_t *>((const uint8_t *)rec + measure_record_zero_offset(P.records));
-    const uint64_t per = P.gpb < 16 ? 256 : 4;   // blocks per workgroup
-    const uint64_t grid = (P.slots + per - 1) / per;
-    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (P.gpb < 16)
-        hipLaunchKernelGGL(k_measure_blocks, dim3((uint32_t)grid), dim3(256), 0, s, rfp, rz, P.slots, P.bpo, P.gpo,
-                           P.gpb, block_bytes, P.last_block, fp, zero_total);
-    else
-        hipLaunchKernelGGL(k_measure_blocks_wave, dim3((uint32_t)grid), dim3(256), 0, s, rfp, rz, P.slots, P.bpo,
-                           P.gpo, P.gpb, block_bytes, P.last_block, fp, zero_total);
-    return hipGetLastError();
+    const uint32_t *rz = record_zeros(rec, P.records);
+    return blocks_launch(P.slots, P.gpb, [&](bool wave, dim3 grid) {
+        hipLaunchKernelGGL((wave ? k_measure_blocks<true> : k_measure_blocks<false>), grid, dim3(256), 0, s, rfp, rz,
+                           P.slots, P.bpo, P.gpo, P.gpb, block_bytes, P.last_block, fp, zero_total);
+    });
 }
 
 uint64_t measure_hist_part_bytes(int cus) { return (uint64_t)hist_grid_max(cus) * 256 * sizeof(uint32_t); }
 
 hipError_t launch_byte_hist(const MeasurePlan &P, const uint8_t *src, uint64_t stride, int cus, void *part,
                             uint64_t *hist, hipStream_t s) {
-    (void)hipGetLastError();
-    const uint64_t gmax = hist_grid_max(cus);
-    const uint32_t grid = (uint32_t)(P.records < gmax ? P.records : gmax);
-    if (P.records > (uint64_t)grid * kHistMaxGranules) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_byte_hist, dim3(grid), dim3(256), 0, s, src, stride, P.len, P.gpo, P.records,
-                       reinterpret_cast<uint32_t *>(part));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_hist_reduce, dim3(1), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(part), grid, hist);
-    return hipGetLastError();
+    return hist_launch(P.records, cus, part, hist, s, [&](dim3 grid, uint32_t *slots) {
+        hipLaunchKernelGGL(k_byte_hist, grid, dim3(256), 0, s, src, stride, P.len, P.gpo, P.records, slots);
+    });
 }
 
 hipError_t launch_measure_granules_batch(const uint8_t *src_base, const SpanTile *tiles, uint64_t ntiles,
@@ -448,18 +437,13 @@ hipError_t launch_measure_granules_batch(const uint8_t *src_base, const SpanTile
                                          hipStream_t s) {
     (void)hipGetLastError();
     MeasureFp *rfp = reinterpret_cast<MeasureFp *>(rec);
-    uint32_t *rz = reinterpret_cast<uint32_t *>((uint8_t *)rec + measure_record_zero_offset(granules));
+    uint32_t *rz = record_zeros(rec, granules);
     const uint64_t subs = span_batch_sub_launches(ntiles, tshift);
     for (uint64_t i = 0; i < subs; ++i) {
         uint64_t t0, nt;
         span_batch_sub_launch(ntiles, tshift, i, &t0, &nt);
-        const dim3 g((uint32_t)(nt << tshift));
-        if (waves == 1)
-            hipLaunchKernelGGL((k_measure_batch<1>), g, dim3(64), 0, s, src_base, tiles, t0, tshift, gpb, rfp, rz);
-        else if (waves == 4)
-            hipLaunchKernelGGL((k_measure_batch<4>), g, dim3(256), 0, s, src_base, tiles, t0, tshift, gpb, rfp, rz);
-        else
-            hipLaunchKernelGGL((k_measure_batch<2>), g, dim3(128), 0, s, src_base, tiles, t0, tshift, gpb, rfp, rz);
+        hipLaunchKernelGGL(MEASURE_FOR_WAVES(k_measure_batch, waves), dim3((uint32_t)(nt << tshift)),
+                           waves_block(waves), 0, s, src_base, tiles, t0, tshift, gpb, rfp, rz);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -469,34 +453,21 @@ hipError_t launch_measure_granules_batch(const uint8_t *src_base, const SpanTile
 hipError_t launch_measure_blocks_batch(const SpanEnt *ents, uint64_t live, uint64_t blocks, uint64_t granules,
                                        uint64_t block_bytes, const void *rec, MeasureFp *fp, uint64_t *zero_total,
                                        hipStream_t s) {
-    (void)hipGetLastError();
     const MeasureFp *rfp = reinterpret_cast<const MeasureFp *>(rec);
-    const uint32_t *rz = reinterpret_cast<const uint32_t *>((const uint8_t *)rec + measure_record_zero_offset(granules));
+    const uint32_t *rz = record_zeros(rec, granules);
     const uint32_t gpb = (uint32_t)(block_bytes / kGran);
-    const uint64_t per = gpb < 16 ? 256 : 4;   // blocks per workgroup, as launch_measure_blocks chooses
-    const uint64_t grid = (blocks + per - 1) / per;
-    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (gpb < 16)
-        hipLaunchKernelGGL((k_measure_blocks_batch<false>), dim3((uint32_t)grid), dim3(256), 0, s, rfp, rz, blocks, ents,
-                           live, gpb, block_bytes, fp, zero_total);
-    else
-        hipLaunchKernelGGL((k_measure_blocks_batch<true>), dim3((uint32_t)grid), dim3(256), 0, s, rfp, rz, blocks, ents,
-                           live, gpb, block_bytes, fp, zero_total);
-    return hipGetLastError();
+    return blocks_launch(blocks, gpb, [&](bool wave, dim3 grid) {
+        hipLaunchKernelGGL((wave ? k_measure_blocks_batch<true> : k_measure_blocks_batch<false>), grid, dim3(256), 0, s,
+                           rfp, rz, blocks, ents, live, gpb, block_bytes, fp, zero_total);
+    });
 }
 
 hipError_t launch_byte_hist_batch(const uint8_t *src_base, const SpanTile *tiles, uint64_t ntiles, uint32_t tshift,
                                   int cus, void *part, uint64_t *hist, hipStream_t s) {
-    (void)hipGetLastError();
-    const uint64_t gmax = hist_grid_max(cus), total = ntiles << tshift;
-    const uint32_t grid = (uint32_t)(total < gmax ? total : gmax);
-    if (total > (uint64_t)grid * kHistMaxGranules) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_byte_hist_batch, dim3(grid), dim3(256), 0, s, src_base, tiles, total, tshift,
-                       reinterpret_cast<uint32_t *>(part));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_hist_reduce, dim3(1), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(part), grid, hist);
-    return hipGetLastError();
+    const uint64_t total = ntiles << tshift;
+    return hist_launch(total, cus, part, hist, s, [&](dim3 grid, uint32_t *slots) {
+        hipLaunchKernelGGL(k_byte_hist_batch, grid, dim3(256), 0, s, src_base, tiles, total, tshift, slots);
+    });
 }
 
 hipError_t launch_measure_distinct(const MeasureFp *fp, uint64_t n, void *work, size_t *tmp_bytes,

@@ -206,19 +206,50 @@ def test_gear_table_or_arithmetic(S, torch, gpu_ctx):
 
 # ---- 2. crafted windows -----------------------------------------------------------------
 
-def test_window_at_every_granule_and_lane_edge(S, torch, gpu_ctx):
-    """The window ends at every offset from 4064 to 4128 of a zero background: the
-    granule's edge, both sides of it, and every lane-run edge near it."""
+@functools.lru_cache(maxsize=None)
+def edge_objects():
+    """(ends, objects, size, stride): the window ends at every offset from 4064 to
+    4128 of a zero background, one object each."""
     w = window13()
     size, stride = 3 * 4096 + 77, 3 * 4096 + 96
     ends = list(range(4064, 4129))
     objs = [zeros_with(size, [e], w) for e in ends]
-    got = gpu_ctx.measure_chunks_stream(dev(torch, strided(objs, stride, 0x5A)), size, len(objs), stride)
-    assert got == restate(S, objs, DEFAULTS)
-    for e, o in zip(ends, objs):                           # one by one: a miss names its offset
-        r = gpu_ctx.measure_chunks(dev(torch, np.concatenate([o, np.full(19, 0x5A, np.uint8)])), size)
-        assert r == restate(S, [o], DEFAULTS), e
-        assert r.candidates >= 1 and r.chunks == 2 and r.forced_cuts == 0
+    for o in objs:
+        o.setflags(write=False)
+    return ends, objs, size, stride
+
+
+def chunked(ctx, table, params, add):
+    """The result of one handle, G from LDS (table) or computed, after add(handle)."""
+    with ctx.chunker(*params) as h:
+        h.gear_table(table)
+        add(h)
+        return h.result()
+
+
+def test_window_at_every_granule_and_lane_edge(S, torch, gpu_ctx):
+    """The window ends at every offset from 4064 to 4128 of a zero background: the
+    granule's edge, both sides of it, and every lane-run edge near it; with G
+    from LDS and with G computed."""
+    ends, objs, size, stride = edge_objects()
+    buf, want = dev(torch, strided(objs, stride, 0x5A)), restate(S, objs, DEFAULTS)
+    ones = [(e, dev(torch, np.concatenate([o, np.full(19, 0x5A, np.uint8)])), restate(S, [o], DEFAULTS))
+            for e, o in zip(ends, objs)]
+    for table in (True, False):
+        got = chunked(gpu_ctx, table, DEFAULTS, lambda h: h.add_stream(buf, size, len(objs), stride))
+        assert got == want, table
+        for e, t, w1 in ones:                              # one by one: a miss names its offset
+            r = chunked(gpu_ctx, table, DEFAULTS, lambda h: h.add(t, size))
+            assert r == w1, (table, e)
+            assert r.candidates >= 1 and r.chunks == 2 and r.forced_cuts == 0
+
+
+def test_window_edges_in_a_batch_with_g_computed(S, torch, gpu_ctx):
+    """The same 65 objects as one batch add, G computed per byte."""
+    ends, objs, size, stride = edge_objects()
+    buf = dev(torch, strided(objs, stride, 0x5A))
+    spans = [(j * stride, size) for j in range(len(objs))]
+    assert chunked(gpu_ctx, False, DEFAULTS, lambda h: h.add_batch(buf, spans)) == restate(S, objs, DEFAULTS)
 
 
 @pytest.mark.parametrize("mn,mx,first", [(2048, 65536, 5000), (2048, 65536, None), (32, 256, None), (100, 1000, 777)],
@@ -332,16 +363,19 @@ def test_ragged_stream_ignores_gaps(S, torch, gpu_ctx, params):
 
 
 def test_tiny_objects(S, torch, gpu_ctx):
-    for v in (0, 57):
-        b = np.full(1, v, np.uint8)
-        r = gpu_ctx.measure_chunks(dev(torch, np.concatenate([b, np.full(15, 0xEE, np.uint8)])), 1, *SMALL)
-        assert r == restate(S, [b], SMALL) == S.ChunkResult(1, 1, 1, 1, 0, 0)
     rng = np.random.default_rng(6)
     objs = [rng.integers(0, 256, 100, dtype=np.uint8) for _ in range(7)]
     objs[5] = objs[2].copy()
-    for params in (SMALL, DEFAULTS):
-        r = gpu_ctx.measure_chunks_stream(dev(torch, strided(objs, 112, 0x11)), 100, 7, 112, *params)
-        assert r == restate(S, objs, params)
+    buf = dev(torch, strided(objs, 112, 0x11))
+    for table in (True, False):                            # G from LDS, G computed
+        for v in (0, 57):
+            b = np.full(1, v, np.uint8)
+            t = dev(torch, np.concatenate([b, np.full(15, 0xEE, np.uint8)]))
+            r = chunked(gpu_ctx, table, SMALL, lambda h: h.add(t, 1))
+            assert r == restate(S, [b], SMALL) == S.ChunkResult(1, 1, 1, 1, 0, 0), (table, v)
+        for params in (SMALL, DEFAULTS):
+            r = chunked(gpu_ctx, table, params, lambda h: h.add_stream(buf, 100, 7, 112))
+            assert r == restate(S, objs, params), (table, params)
 
 
 def test_stream_across_object_split(S, torch, gpu_ctx):

@@ -600,6 +600,41 @@ def test_odd_block_edge_sizes(S, torch, wave_ctx, block_bytes, waves):
         assert ctx.measure(dev(torch, a), block_bytes=bb) == want, size
 
 
+@functools.lru_cache(maxsize=None)
+def switch_objects(block_bytes):
+    """Five objects of two full blocks and a ragged third of 4096 + 5 bytes: random, but for
+    a block shared by two objects, a run of zeros and two equal ragged blocks."""
+    rng = np.random.default_rng(4200 + block_bytes)
+    objs = [rng.integers(0, 256, 2 * block_bytes + 4096 + 5, dtype=np.uint8) for _ in range(5)]
+    objs[1][:block_bytes] = objs[0][:block_bytes]
+    objs[2][block_bytes + 100:block_bytes + 5100] = 0
+    objs[4][2 * block_bytes:] = objs[3][2 * block_bytes:]
+    for a in objs:
+        a.setflags(write=False)
+    return objs
+
+
+@pytest.mark.parametrize("form", ["stream", "batch"])
+@pytest.mark.parametrize("block_bytes", [15 * 4096, 16 * 4096])
+def test_pass2_at_the_thread_wave_switch(S, torch, gpu_ctx, block_bytes, form):
+    """Blocks of 15 granules (the last size summed by one thread) and of 16 (the first summed by
+    one wave), through add_stream and add_batch: 15 blocks, so the wave form's last workgroup of
+    four holds three."""
+    objs = switch_objects(block_bytes)
+    size = objs[0].size
+    stride = -(-(size + 4096 + 12) // 16) * 16
+    want = expect(S, objs, block_bytes, hist=True)
+    assert (want.bytes, want.blocks, want.unique_blocks) == (5 * size, 15, 13)
+    assert want.zero_bytes >= 5000
+    t = dev(torch, strided(objs, stride, 0xA5))
+    with gpu_ctx.measurer(block_bytes, hist=True) as m:
+        if form == "stream":
+            m.add_stream(t, size, 5, stride)
+        else:
+            m.add_batch(t, [(j * stride, size) for j in range(5)])
+        assert m.result() == want
+
+
 # ---- 10. every piece enters the fingerprint, under a key of its own ---------------------------------
 
 def piece_set(block_bytes):
