@@ -354,6 +354,51 @@ int s3dg_verify_dgen_stream(s3dg_ctx *ctx, const void *src, uint64_t obj_size, u
                             uint64_t seed_base, uint64_t first_obj, void *stream,
                             s3dg_verify_result *out);
 
+/* ---- a mixed-size batch of DG1 objects in one call ------
+ * The DG1 forms of s3dg_fill_controlled_batch / s3dg_verify_controlled_batch.
+ * s3dg_obj_desc is read for DG1: dst_off = the object's byte offset from the
+ * base pointer (a multiple of 16); size = its bytes; entropy = its DG1 seed,
+ * the `seed` argument of s3dg_dgen_fill (s3dg_dgen_fill_stream's object j:
+ * s3dg_object_entropy(seed_base, j)); dedup: U = s3dg_unique_blocks(ceil(size /
+ * 1 MiB), dedup), per object; f_num / f_den: the zero prefix of every 1 MiB
+ * block, floor(L * f_num / f_den).
+ *
+ * s3dg_dgen_fill_batch: object k's bytes are exactly those of
+ * s3dg_dgen_fill(ctx, dst_base + dst_off, size, 0, ~0, dedup, f_num, f_den,
+ * entropy, stream).  Asynchronous and stream-ordered; `descs` is consumed
+ * before return.  Nothing outside the objects is written: no gap byte, nothing
+ * past an object's end.  Overlapping destinations are the caller's business.
+ *
+ * s3dg_verify_dgen_batch finds what s3dg_verify_dgen finds on the same bytes,
+ * under s3dg_verify_controlled_batch's rules: synchronous on `stream`; nothing
+ * is written to the payload and no byte at or past an object's end is read;
+ * descriptors may come in any order, leave gaps, overlap and repeat, and empty
+ * objects are allowed anywhere.  *out (totals; required) sums
+ * mismatched_bytes and mismatched_blocks over the descriptors (a byte that is
+ * wrong for two descriptors counts twice), blocks being 4 KiB granules aligned
+ * within each object; first_offset is the lowest differing offset from
+ * src_base.  per_obj (host array of n, or NULL): the same for descriptor k,
+ * first_offset counted from that object's first byte; an empty object is clean,
+ * {0, 0, UINT64_MAX}.  `out` and `per_obj` are written only on success.
+ *
+ * Both calls check every descriptor before the first launch, so a refused
+ * call has written or read nothing.  Refusals (S3DG_EINVAL, each with a
+ * message): a null `out` of the verify ("null output"); null `descs` with
+ * n > 0 ("null descriptor array"); a null or not 16-byte aligned base pointer
+ * ("dst_base / src_base must be 16-byte aligned"); and for the first offending
+ * non-empty descriptor k, "object k: " followed by "dst_off must be a multiple
+ * of 16", "need f_num < f_den" (f_den == 0 included) or "object larger than
+ * 2^32 blocks".  n == 0, or only empty objects, launches nothing and succeeds.
+ * Calls on different streams of one context share no state; two threads on two
+ * streams are safe.  The lanes follow s3dg_set_keystream_shape(mode 1) as the
+ * other DG1 calls do; the bytes and the results do not depend on it. */
+int s3dg_dgen_fill_batch(s3dg_ctx *ctx, void *dst_base,
+                         const s3dg_obj_desc *descs, uint64_t n, void *stream);
+int s3dg_verify_dgen_batch(s3dg_ctx *ctx, const void *src_base,
+                           const s3dg_obj_desc *descs, uint64_t n, void *stream,
+                           s3dg_verify_result *out,       /* totals; required */
+                           s3dg_verify_result *per_obj);  /* host array of n, or NULL */
+
 /* ---- measurement (read-only) ------------------------------
  * What a payload is worth to a store that deduplicates and compresses at
  * `block_bytes`: how many of its blocks are distinct and how many of its bytes

@@ -127,6 +127,9 @@ SIGNATURES = {
                                  ctypes.POINTER(VerifyRec)]),
     "s3dg_verify_dgen_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_u64, c_u32, c_u32, c_u64, c_u64, c_vp,
                                         ctypes.POINTER(VerifyRec)]),
+    "s3dg_dgen_fill_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(ObjDesc), c_u64, c_vp]),
+    "s3dg_verify_dgen_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(ObjDesc), c_u64, c_vp,
+                                       ctypes.POINTER(VerifyRec), ctypes.POINTER(VerifyRec)]),
     "s3dg_measure_create": (c_int, [c_vp, c_u64, c_int, ctypes.POINTER(c_vp)]),
     "s3dg_measure_destroy": (c_int, [c_vp]),
     "s3dg_measure_reset": (c_int, [c_vp]),

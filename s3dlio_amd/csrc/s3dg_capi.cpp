@@ -118,6 +118,11 @@ void stream_state_free(StreamState *S) {
         if (e) (void)hipEventDestroy(e);
     if (S->ks.dev) (void)hipFree(S->ks.dev);
     if (S->vobj) (void)hipFree(S->vobj);
+    for (auto &T : S->dtab) {
+        if (T.host) (void)hipHostFree(T.host);
+        if (T.dev) (void)hipFree(T.dev);
+        if (T.uploaded) (void)hipEventDestroy(T.uploaded);
+    }
     delete S;
 }
 

@@ -2,6 +2,7 @@
 // state and the measured defaults.  Private to the units that implement
 // include/s3dlio_gpu.h over the context (s3dg_capi.cpp, s3dg_tune.cpp,
 // s3dg_fill.cpp, s3dg_batchfill.cpp, s3dg_verify_batch.cpp, s3dg_keystream.cpp,
+// s3dg_dgen_batch.cpp,
 // and, through s3dg_accum.h, s3dg_measure.cpp, s3dg_chunks.cpp and
 // s3dg_lz.cpp); everything else
 // reaches a context through the functions of s3dg_internal.h.
@@ -191,6 +192,16 @@ struct StreamState {
     uint64_t vobj_cap = 0;
     // queue counters of persistent keystream launches on this stream
     KsCounters ks;
+    // chunk-record tables of DG1 batch calls (s3dg_dgen_batch.cpp): two sets,
+    // so the host builds call k+1's records while call k's upload is pending.
+    // The upload and the launches that read the device table are all on the
+    // stream, which orders them; `uploaded` frees the pinned host side.
+    struct DgenTable {
+        DgenChunkRec *host = nullptr, *dev = nullptr;
+        uint64_t cap = 0;
+        hipEvent_t uploaded = nullptr;
+    } dtab[2];
+    int dnext = 0;
     // lifetime (under the context's mu): users holding the state, and whether
     // s3dg_stream_release has taken it out of the context's map; the last
     // holder of a released state drains the stream and frees it
@@ -330,6 +341,10 @@ void tune_mark(s3dg_ctx *c, int zc, const ZcTuner::Pending &probe, bool end, hip
 // copied back, the stream drained, the record returned to the list.
 int verify_with_record(s3dg_ctx *c, hipStream_t s, const char *launch_what,
                        const std::function<hipError_t(VerifyRec *)> &launch, s3dg_verify_result *out);
+
+// The device jump table of lanes sub < lpc starting at draws z0 + sub*span,
+// from the context's cache (s3dg_keystream.cpp).
+int jump_table(s3dg_ctx *c, uint32_t lpc, uint64_t span, uint64_t z0, const uint64_t **jtab);
 
 // A record map of at least `tiles` records in place of *map (s3dg_fill.cpp).
 // The caller has waited for every launch that reads the old one.

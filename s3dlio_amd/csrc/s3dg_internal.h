@@ -9,6 +9,7 @@
 #include "s3dlio_gpu.h"
 #include "s3dg_batch_plan.h"   // kBlk, the batch tile-shift range
 #include "s3dg_verify_batch_plan.h"
+#include "s3dg_dgen_batch_plan.h"   // DgenChunkRec, the batch's lane limits
 
 // Sets the calling thread's error text (s3dg_last_error) and returns code.
 extern "C" int s3dg_internal_fail(int code, const char *msg);
@@ -232,6 +233,19 @@ hipError_t keystream_occupancy(const KsShape &sh, int *wgs_per_cu);
 // launch adds to it, off0 is added to every reported offset.
 hipError_t launch_verify_keystream(const uint8_t *src, const KeystreamArgs &A, const uint64_t *jtab, uint64_t off0,
                                    VerifyRec *rec, hipStream_t s);
+
+// A mixed-size DG1 batch (k_keystream_batch / k_verify_keystream_batch,
+// DESIGN.md §5.3.1): the nrec chunk records at recs (device) are one size
+// class of a call, each chunk over lpc lanes of `span` draws (dgen_class_lanes),
+// jtab = the jump table of (lpc, span, z0 = 0).  The fill follows sh as
+// launch_keystream's static grid does; the verify adds to *tot (offsets from
+// src) and, when pobj is not null, to pobj[record's obj] (offsets from the
+// object's first byte), both reset by the caller on the stream first.
+hipError_t launch_keystream_batch(uint8_t *dst, const DgenChunkRec *recs, uint64_t nrec, uint32_t lpc, uint64_t span,
+                                  const uint64_t *jtab, const KsShape &sh, hipStream_t s);
+hipError_t launch_verify_keystream_batch(const uint8_t *src, const DgenChunkRec *recs, uint64_t nrec, uint32_t lpc,
+                                         uint64_t span, const uint64_t *jtab, VerifyRec *tot, VerifyRec *pobj,
+                                         hipStream_t s);
 
 // thr/nthr: records for the tiled shape's trailing loads (lc.prefetch_tiles), or null
 hipError_t launch_write_ceiling(const LaunchCfg &lc, uint8_t *dst, uint64_t len,

@@ -904,6 +904,36 @@ __device__ __forceinline__ uint64_t ks_remap(const KeystreamArgs &A, uint64_t b)
     return b;
 }
 
+// A lane's header: where its chunk lies, how long it and its zero prefix are,
+// and the chunk's seed input.  The uniform launches derive it from the
+// launch's arguments, in ks_unit itself; the batch launches read it from the
+// record table (ks_header_batch).  obj / delta serve the batch verify alone.
+struct KsHeader {
+    uint64_t coff;    // the chunk's byte offset within dst
+    uint64_t clen;    // its length; 0: no chunk for this lane
+    uint64_t zlen;    // its zero prefix
+    uint64_t x;       // seed input of its xoshiro state
+    uint32_t obj;     // the object's index
+    uint64_t delta;   // (offset within the object) - (offset within dst), mod 2^64
+};
+
+// Chunk c of a batch launch: record c of the launch's nrec (s3dg_dgen_batch_plan.h).
+// A lane past the table reads nothing and has no chunk.
+__device__ __forceinline__ KsHeader ks_header_batch(const DgenChunkRec *recs, uint64_t nrec, uint64_t c) {
+    KsHeader H{0, 0, 0, 0, 0, 0};
+    if (c < nrec) {
+        const uint4 *rp = reinterpret_cast<const uint4 *>(recs + c);
+        const uint4 r0 = rp[0], r1 = rp[1];
+        H.coff = ((uint64_t)r0.y << 32) | r0.x;
+        H.x = ((uint64_t)r0.w << 32) | r0.z;
+        H.clen = r1.x;
+        H.zlen = r1.y;
+        H.obj = r1.z;
+        H.delta = (uint64_t)r1.w * kDgenBlock - H.coff;
+    }
+    return H;
+}
+
 // One work unit: wave w of remapped workgroup bid, i.e. lanes
 // [(bid*W + w)*64, +64) of the launch.  myrows: this wave's LDS rows.
 //
@@ -921,10 +951,22 @@ __device__ __forceinline__ uint64_t ks_remap(const KeystreamArgs &A, uint64_t b)
 // added to the unit's granule count when the granule closes.  Only a unit that
 // found a difference touches rec, from lane 0: two 64-bit adds and a 64-bit
 // min (vector atomics); off0 is added to the reported offset.
-template <int D, int W, int SP, bool V = false>
+//
+// B (k_keystream_batch, k_verify_keystream_batch): the header comes from the
+// record table and, in the verify, differences are also counted per object:
+// a wave may hold lanes of several objects, so a lane that found a difference
+// adds its bytes and its lowest offset to the record of the object that owns
+// the ROW the piece came from (its index and offset shuffled from the row's
+// lane), and when a granule closes the lane of every row marked in vmask adds
+// one granule to its own object.  All of it sits behind the stage's vote: the
+// clean path still has no store and no atomic.  The totals go through
+// v_finish as before.
+template <int D, int W, int SP, bool V = false, bool B = false>
 __device__ __forceinline__ void ks_unit(uint8_t *dst, const KeystreamArgs &A, const uint64_t *jtab,
                                         uint8_t *myrows, uint32_t l, uint64_t bid, uint32_t w,
-                                        VerifyRec *rec = nullptr, uint64_t off0 = 0) {
+                                        VerifyRec *rec = nullptr, uint64_t off0 = 0,
+                                        const DgenChunkRec *recs = nullptr, uint64_t nrec = 0,
+                                        VerifyRec *pobj = nullptr) {
     static_assert(D == 16 || D == 32 || D == 64, "draws per stage");
     constexpr int RS = D * 8 + 16;     // row stride: + 16 B pad, conflict-light ds_write_b128 rows
     constexpr int P = D / 2;           // 16-byte pieces per row
@@ -938,33 +980,45 @@ __device__ __forceinline__ void ks_unit(uint8_t *dst, const KeystreamArgs &A, co
     const uint32_t lsh = (uint32_t)__builtin_ctz(lpc);
     const uint64_t gl = (bid * W + w) * 64 + l;
     const uint64_t c = gl >> lsh;                                    // local chunk index
-    const uint64_t cpo = A.cpo ? A.cpo : A.nchunks;
-    const uint64_t ko = c / cpo;                                     // object within the launch
-    const uint64_t cl = c - ko * cpo;
-    const uint64_t cg = A.chunk0 + cl;                               // chunk index in the object
     const uint32_t sub = (uint32_t)(gl & (lpc - 1));
-    const uint64_t coff = A.doff + ko * A.obj_stride + cl * A.chunk_bytes;   // offset within dst
-    const uint64_t seed_base = A.seed_base + ko * A.seed_step;
-    const uint64_t gofs = cg * A.chunk_bytes;                        // offset within the object
-    const uint64_t clen = (c < A.nchunks && gofs < A.obj_len)
-                              ? ((A.obj_len - gofs) < A.chunk_bytes ? (A.obj_len - gofs) : A.chunk_bytes)
-                              : 0;
+    KsHeader H{0, 0, 0, 0, 0, 0};
+    uint64_t cg = 0, seed_base = 0, coff, clen;
+    if constexpr (B) {
+        H = ks_header_batch(recs, nrec, c);
+        coff = H.coff;
+        clen = H.clen;
+    } else {
+        const uint64_t cpo = A.cpo ? A.cpo : A.nchunks;
+        const uint64_t ko = c / cpo;                                     // object within the launch
+        const uint64_t cl = c - ko * cpo;
+        cg = A.chunk0 + cl;                                              // chunk index in the object
+        coff = A.doff + ko * A.obj_stride + cl * A.chunk_bytes;          // offset within dst
+        seed_base = A.seed_base + ko * A.seed_step;
+        const uint64_t gofs = cg * A.chunk_bytes;                        // offset within the object
+        clen = (c < A.nchunks && gofs < A.obj_len)
+                   ? ((A.obj_len - gofs) < A.chunk_bytes ? (A.obj_len - gofs) : A.chunk_bytes)
+                   : 0;
+    }
     const uint64_t d0 = A.z0 + (uint64_t)sub * span;                 // first draw index
     const uint64_t rb = d0 * 8;                                      // lane region within chunk
     const uint32_t rlen = (uint32_t)(clen > rb ? ((clen - rb) < (uint64_t)span * 8 ? (clen - rb) : (uint64_t)span * 8) : 0);
     const uint64_t tail_draw = clen >> 3;                            // draw index of a 1..7 B tail
     const bool tail_hi = (clen & 7) >= 1 && (clen & 7) <= 4;         // next_u32 = next_u64 >> 32
     // zero prefix of the chunk (dgen-contract compressibility); 0 for the npz fill
-    const uint64_t zlen = A.zf_num ? (clen * A.zf_num) / A.zf_den : 0;
-
-    // chunk seed: npz.rs:381 seed_from_u64(k), or the dgen mode
-    // seed ^ (u * phi) with u = chunk % U (dedup)
-    uint64_t x;
-    if (A.seed_mode == 0) {
-        x = seed_base + cg;
+    uint64_t zlen, x;
+    if constexpr (B) {
+        zlen = H.zlen;
+        x = H.x;
     } else {
-        const uint32_t u = A.unique == 0xFFFFFFFFu ? (uint32_t)cg : fastmod((uint32_t)cg, A.m_unique, A.unique);
-        x = seed_base ^ ((uint64_t)u * 0x9E3779B97F4A7C15ull);
+        zlen = A.zf_num ? (clen * A.zf_num) / A.zf_den : 0;
+        // chunk seed: npz.rs:381 seed_from_u64(k), or the dgen mode
+        // seed ^ (u * phi) with u = chunk % U (dedup)
+        if (A.seed_mode == 0) {
+            x = seed_base + cg;
+        } else {
+            const uint32_t u = A.unique == 0xFFFFFFFFu ? (uint32_t)cg : fastmod((uint32_t)cg, A.m_unique, A.unique);
+            x = seed_base ^ ((uint64_t)u * 0x9E3779B97F4A7C15ull);
+        }
     }
     uint64_t s0 = mix64(x + 0x9E3779B97F4A7C15ull), s1 = mix64(x + 2 * 0x9E3779B97F4A7C15ull);
     uint64_t s2 = mix64(x + 3 * 0x9E3779B97F4A7C15ull), s3 = mix64(x + 4 * 0x9E3779B97F4A7C15ull);
@@ -1035,17 +1089,34 @@ __device__ __forceinline__ void ks_unit(uint8_t *dst, const KeystreamArgs &A, co
 #pragma unroll
                 for (int j = 0; j < R; ++j)
                     if ((bal >> (j * P)) & (~0ull >> (64 - P))) vmask |= 1ull << (R * i + j);
+                uint32_t robj = 0;                        // B: the row's object and offset within it
+                uint64_t rdelta = 0;
+                if constexpr (B) {
+                    robj = __shfl(H.obj, (int)(R * i + l / P));
+                    rdelta = __shfl(H.delta, (int)(R * i + l / P));
+                }
                 if (d) {
                     uint32_t c = 0, f = 16;
                     diff_piece(g[i], 0, c, f);
                     vcnt += c;
                     const uint64_t pos = off0 + raddr[i] + o + f;
                     vfirst = pos < vfirst ? pos : vfirst;
+                    if constexpr (B) {
+                        if (pobj) {
+                            atomicAdd(reinterpret_cast<unsigned long long *>(&pobj[robj].bytes), (unsigned long long)c);
+                            atomicMin(reinterpret_cast<unsigned long long *>(&pobj[robj].first),
+                                      (unsigned long long)(raddr[i] + rdelta + o + f));
+                        }
+                    }
                 }
             }
         }
         constexpr uint32_t GS = kBlk / (D * 8);           // stages per 4 KiB granule of a row
         if ((it + 1) % GS == 0 || it + 1 == iters) {
+            if constexpr (B) {
+                if (pobj && ((vmask >> l) & 1ull))
+                    atomicAdd(reinterpret_cast<unsigned long long *>(&pobj[H.obj].blocks), 1ull);
+            }
             vblocks += (uint32_t)__builtin_popcountll(vmask);
             vmask = 0;
         }
@@ -1348,6 +1419,33 @@ __global__ __launch_bounds__(64) void k_verify_keystream(const uint8_t *src, Key
                                      off0);
 }
 
+// A mixed-size DG1 batch (s3dg_dgen_fill_batch): k_keystream's
+// static grid with the lanes' headers read from a record table, one record per
+// chunk of the launch's size class (A: lpc, span, xg, nwg; z0 = 0).  Zero
+// prefixes are written inside the lanes.
+template <int D, int W, int SP>
+__global__ __launch_bounds__(64 * W) void k_keystream_batch(uint8_t *dst, KeystreamArgs A, const uint64_t *jtab,
+                                                            const DgenChunkRec *recs, uint64_t nrec) {
+    constexpr int RS = D * 8 + 16;
+    __shared__ __attribute__((aligned(16))) uint8_t rows[W][64 * RS];
+    const uint32_t t = threadIdx.x, l = t & 63;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(t >> 6);
+    ks_unit<D, W, SP, false, true>(dst, A, jtab, rows[w], l, ks_remap(A, blockIdx.x), w, nullptr, 0, recs, nrec);
+}
+
+// Its read-side twin (s3dg_verify_dgen_batch): k_verify_keystream over the
+// record table.  tot takes the launch's totals (offsets from src), pobj (or
+// null) the per-object records (offsets from each object's first byte).
+template <int D>
+__global__ __launch_bounds__(64) void k_verify_keystream_batch(const uint8_t *src, KeystreamArgs A,
+                                                               const uint64_t *jtab, const DgenChunkRec *recs,
+                                                               uint64_t nrec, VerifyRec *tot, VerifyRec *pobj) {
+    constexpr int RS = D * 8 + 16;
+    __shared__ __attribute__((aligned(16))) uint8_t rows[64 * RS];
+    ks_unit<D, 1, kStorePlain, true, true>(const_cast<uint8_t *>(src), A, jtab, rows, threadIdx.x & 63, blockIdx.x, 0,
+                                           tot, 0, recs, nrec, pobj);
+}
+
 // DG1 zero prefixes in the fill's store shape (paired with a keystream launch
 // over the chunks' tails, s3dg_internal_dgen_chunk): one 64-thread workgroup
 // per 4 KiB granule, four 16-byte zero stores per lane (1 KiB per
@@ -1403,6 +1501,21 @@ hipError_t launch_ks_one(uint8_t *dst, const KeystreamArgs &A, const uint64_t *j
         hipLaunchKernelGGL((k_keystream<D, W, kStoreNT>), g, t, lds, s, dst, A, jtab, A2, jtab2);
     else
         hipLaunchKernelGGL((k_keystream<D, W, kStorePlain>), g, t, lds, s, dst, A, jtab, A2, jtab2);
+    return hipGetLastError();
+}
+
+template <int D, int W>
+hipError_t launch_ksb_one(uint8_t *dst, const KeystreamArgs &A, const uint64_t *jtab, uint32_t lds, int store,
+                          hipStream_t s, uint64_t wgs, const DgenChunkRec *recs, uint64_t nrec) {
+    const dim3 g((uint32_t)wgs), t(64 * W);
+    if (store == kStoreSC1)
+        hipLaunchKernelGGL((k_keystream_batch<D, W, kStoreSC1>), g, t, lds, s, dst, A, jtab, recs, nrec);
+    else if (store == kStoreNTSC1)
+        hipLaunchKernelGGL((k_keystream_batch<D, W, kStoreNTSC1>), g, t, lds, s, dst, A, jtab, recs, nrec);
+    else if (store == kStoreNT)
+        hipLaunchKernelGGL((k_keystream_batch<D, W, kStoreNT>), g, t, lds, s, dst, A, jtab, recs, nrec);
+    else
+        hipLaunchKernelGGL((k_keystream_batch<D, W, kStorePlain>), g, t, lds, s, dst, A, jtab, recs, nrec);
     return hipGetLastError();
 }
 
@@ -1807,6 +1920,50 @@ hipError_t launch_verify_keystream(const uint8_t *src, const KeystreamArgs &A0, 
     A.ctr = nullptr;
     A.par = 0;
     hipLaunchKernelGGL((k_verify_keystream<64>), dim3((uint32_t)waves), dim3(64), 0, s, src, A, jtab, off0, rec);
+    return hipGetLastError();
+}
+
+// The lanes of a batch launch: nrec chunks x lpc lanes of `span` draws, as a
+// static grid of `waves`-wave workgroups.  false: beyond the grid's reach.
+static bool ksb_args(KeystreamArgs &A, uint32_t lpc, uint64_t span, uint64_t nrec, int waves, uint32_t xg,
+                     uint64_t *wgs) {
+    if (lpc == 0 || (lpc & (lpc - 1)) || span == 0 || span > 0xFFFFFFFFull || nrec > kDgbMaxLanes / lpc) return false;
+    A = KeystreamArgs{};
+    A.lpc = lpc;
+    A.span = (uint32_t)span;
+    A.nchunks = nrec;
+    const uint64_t wv = (nrec * lpc + 63) / 64;
+    *wgs = (wv + (uint64_t)waves - 1) / (uint64_t)waves;
+    A.xg = xg;
+    A.nwg = (uint32_t)*wgs;
+    return true;
+}
+
+hipError_t launch_keystream_batch(uint8_t *dst, const DgenChunkRec *recs, uint64_t nrec, uint32_t lpc, uint64_t span,
+                                  const uint64_t *jtab, const KsShape &sh, hipStream_t s) {
+    (void)hipGetLastError();
+    if (nrec == 0) return hipSuccess;
+    KeystreamArgs A;
+    uint64_t wgs = 0;
+    const uint32_t xg = sh.xcd_waves > sh.waves ? (uint32_t)(sh.xcd_waves / sh.waves) : 1u;
+    if (span % (uint64_t)sh.draws || !ksb_args(A, lpc, span, nrec, sh.waves, xg, &wgs)) return hipErrorInvalidValue;
+    const uint32_t lds = occupancy_lds(sh.wgs_per_cu, ks_static_lds(sh.draws, sh.waves));
+    hipError_t e;
+    S3DG_KS_DISPATCH(e, launch_ksb_one, sh, dst, A, jtab, lds, sh.store, s, wgs, recs, nrec);
+    return e;
+}
+
+hipError_t launch_verify_keystream_batch(const uint8_t *src, const DgenChunkRec *recs, uint64_t nrec, uint32_t lpc,
+                                         uint64_t span, const uint64_t *jtab, VerifyRec *tot, VerifyRec *pobj,
+                                         hipStream_t s) {
+    (void)hipGetLastError();
+    if (nrec == 0) return hipSuccess;
+    KeystreamArgs A;
+    uint64_t wgs = 0;
+    // lane regions of whole granules, 64-draw stages, 1-wave workgroups in dealing order
+    if (span % (kBlk / 8) || !ksb_args(A, lpc, span, nrec, 1, 1, &wgs)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_verify_keystream_batch<64>), dim3((uint32_t)wgs), dim3(64), 0, s, src, A, jtab, recs, nrec,
+                       tot, pobj);
     return hipGetLastError();
 }
 

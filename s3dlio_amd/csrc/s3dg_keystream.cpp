@@ -10,7 +10,7 @@ using namespace s3dg;
 // lanes per chunk + draws per lane for a chunk size; jump table cached per ctx
 // The device jump table of lanes sub < lpc starting at draws z0 + sub*span
 // (cached per context): jtab[sub] = x^(z0 + sub*span) mod P.
-static int jump_table(s3dg_ctx *c, uint32_t lpc, uint64_t span, uint64_t z0, const uint64_t **jtab) {
+int s3dg::jump_table(s3dg_ctx *c, uint32_t lpc, uint64_t span, uint64_t z0, const uint64_t **jtab) {
     std::lock_guard<std::mutex> g(c->mu);
     const std::pair<uint64_t, uint64_t> key{((uint64_t)lpc << 32) | span, z0};
     auto it = c->jtabs.find(key);

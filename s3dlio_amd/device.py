@@ -634,6 +634,52 @@ class Context:
              int(dedup), fn, fd, int(seed_base) & (2**64 - 1), int(first_obj), self._s(stream), ctypes.byref(r))
         return VerifyResult._of(r)
 
+    # -- a mixed-size batch of DG1 objects in one call -----------------------------
+    def _dgen_descs(self, objects):
+        """(descriptor array, n, bytes of the buffer the non-empty objects reach)
+        of fill_batch's `objects`, the entropy read as the object's DG1 seed."""
+        objs = list(objects)
+        arr = (ObjDesc * max(1, len(objs)))()
+        need = 0
+        for k, (off, size, seed, dd, comp) in enumerate(objs):
+            off, size = int(off), int(size)
+            if off < 0 or size < 0 or off >= 2**64 or size >= 2**64:
+                raise ValueError(f"object {k}: offset and size must fit 64 unsigned bits")
+            fn, fd = compress_ratio(comp)
+            arr[k] = ObjDesc(off, size, int(seed) & (2**64 - 1), int(dd), fn, fd)
+            if size:
+                need = max(need, off + size)
+        return arr, len(objs), need
+
+    def dgen_fill_batch(self, dst, objects, stream=None) -> None:
+        """DG1 objects of mixed sizes in one call: objects is fill_batch's
+        iterable of (off, size, seed, dedup, compress), object k being
+        dgen_fill's bytes for (size, dedup, compress, seed) at dst + off.
+        Bounds are checked against `dst` here (ValueError); the library checks
+        every descriptor before its first launch, so a call that raises has
+        written nothing."""
+        arr, n, need = self._dgen_descs(objects)
+        call("s3dg_dgen_fill_batch", self._h, self._dst(dst, need), arr, n, self._s(stream))
+
+    def verify_dgen_batch(self, src, objects, stream=None, per_object: bool = True) -> BatchVerifyResult:
+        """The read-side twin of dgen_fill_batch, with verify_batch's result:
+        totals (first_offset from src) and, per_object, the dirty objects as
+        (index, VerifyResult) with first_offset from the object's first byte.
+        Descriptors may come in any order, leave gaps, overlap and repeat."""
+        arr, n, need = self._dgen_descs(objects)
+        tot = _lib.VerifyRec()
+        per = (_lib.VerifyRec * max(1, n))() if per_object else None
+        call("s3dg_verify_dgen_batch", self._h, self._src(src, need), arr, n, self._s(stream),
+             ctypes.byref(tot), per)
+        mism = None
+        if per_object:
+            mism = ()
+            if tot.mismatched_bytes:
+                a = np.frombuffer(per, dtype=np.uint64, count=3 * n).reshape(-1, 3)
+                mism = tuple((int(k), VerifyResult(int(a[k, 0]), int(a[k, 1]), int(a[k, 2])))
+                             for k in np.flatnonzero(a[:, 0]))
+        return BatchVerifyResult(VerifyResult._of(tot), n, mism)
+
     # -- measurement (read-only) ---------------------------------------------------
     # How many blocks of `block_bytes` are distinct and how many bytes are zero
     # (hist=True: the byte histogram too), whatever wrote the bytes: no seed is
