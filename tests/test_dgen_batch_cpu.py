@@ -1,8 +1,9 @@
 """CPU: the DG1 batch surface without a GPU: the call's plan
 (csrc/s3dg_dgen_batch_plan.h, compiled with g++ alone, plain and under the
 address and undefined-behaviour sanitizers) over a sweep of descriptor lists,
-the C entry points seen from a C program, and the Python methods' bounds
-checks."""
+the C entry points seen from a C program, the Python methods' bounds
+checks, and the lists of tests/dgen_batch_cases.py: its restatement of the
+plan against the header, line by line, and every builder's coverage."""
 import os
 import shutil
 import subprocess
@@ -152,3 +153,123 @@ def test_python_bounds_checks():
     with pytest.raises(ValueError, match="beyond|writes"):
         ctx.dgen_fill_batch(t, [(2**64 - 16, 32, 1, 1, 1)])
     ctx._h = None                                                     # nothing for __del__ to close
+
+
+# ---- the plan restated in Python, and the lists built from it --------------------------------
+
+def _table_lines():
+    """tests/capi/dgen_batch_lanes_table.cpp's output, from the restatement."""
+    import dgen_batch_cases as K
+    out = []
+    lens = [1, 2, K.MIB, K.MIB + 1, 5 * K.MIB]
+    for cls in K.RAGGED:
+        C = 4096 << cls
+        lens += [C // 2, C // 2 + 1, C - 1, C, C + 1]
+    for ln in lens:
+        out.append(f"class {ln} {K.chunk_class(ln)} {K.class_ceiling(K.chunk_class(ln))}")
+    knobs = (0, 512, 4096, 131072)
+    for cls in range(K.FULL + 1):
+        for knob in knobs:
+            for zeros in (0, 1):
+                for draws in (16, 32, 64):
+                    for verify in (0, 1):
+                        for nchunks in (1, 67, 20000):
+                            for cus in (1, 256, 304):
+                                lpc, span = K.class_lanes(K.class_ceiling(cls), nchunks, cus, knob, bool(zeros), draws,
+                                                          bool(verify))
+                                out.append(f"lanes {cls} {knob} {zeros} {draws} {verify} {nchunks} {cus} {lpc} {span}")
+    for cls in range(K.FULL + 1):
+        C = K.class_ceiling(cls)
+        lo = 0 if cls in (0, K.FULL) else C // 2
+        for knob in knobs:
+            for verify in (False, True):
+                lpc, span = K.class_lanes(C, 67, 256, knob, False, 16, verify)
+                for ln in (lo + 1, lo + 17, (lo + C) // 2 + 5, C - 1, C):
+                    if cls == K.FULL and ln != C:
+                        continue
+                    for sub in range(lpc):
+                        rb, rlen = K.lane_region(ln, span, sub)
+                        out.append(f"region {ln} {span} {sub} {rb} {rlen}")
+    return out
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan-ubsan"])
+def test_restatement_equals_the_header(tmp_path, sanitize):
+    """tests/dgen_batch_cases.py restates the size classes, the lane plan (fill
+    and verify, knob set and unset, with and without zero prefixes, every stage
+    width) and the lane regions; tests/capi/dgen_batch_lanes_table.cpp prints
+    the header's.  Every line is equal."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no C++ compiler available")
+    exe = str(tmp_path / "table")
+    extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", *extra,
+                           "-I", os.path.join(ROOT, "s3dlio_amd", "csrc"), "-I", os.path.dirname(HEADER), "-o", exe,
+                           os.path.join(ROOT, "tests", "capi", "dgen_batch_lanes_table.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got, want = out.stdout.splitlines(), _table_lines()
+    assert len(want) > 4320 and len(got) == len(want)
+    for g, w in zip(got, want):
+        assert g == w
+
+
+def test_restated_ratio_is_the_library_s():
+    import dgen_batch_cases as K
+    import s3dlio_amd as S
+    for comp in (0, 1, 2, 3, 7, (3, 2), 1.5):
+        assert K.ratio(comp) == S.compress_ratio(comp), comp
+
+
+def test_knob_lanes():
+    """At the three knobs the builders target, a class of ceiling C has
+    max(1, C / 8 / knob) lanes per chunk: lanes of C, 32 KiB and 4 KiB."""
+    import dgen_batch_cases as K
+    for cls in range(K.FULL + 1):
+        C = K.class_ceiling(cls)
+        assert [K.knob_lanes(cls, k)[1] for k in K.KNOBS] == [C, min(C, 32768), 4096]
+    assert K.list_knob(2048) == 512 and all(K.list_knob(k) == k for k in K.KNOBS)
+
+
+def test_builders_hold_their_coverage():
+    """Every builder at every class and knob: each asserts its own coverage from
+    the restated plan and the byte budget of its list (64 MiB of object bytes).
+    Together every ragged class and the full class are launched at every knob."""
+    import dgen_batch_cases as K
+    for knob in K.KNOBS:
+        launched = set()
+        for cls in K.RAGGED:
+            lists = [K.class_lengths(cls, knob), K.shared_wave(cls, knob)]
+            if cls >= 1:
+                lists.append(K.prefix_ends(cls, knob))
+            for objs, total in lists:
+                assert K.object_bytes(objs) <= K.BUDGET and total >= max(o[0] + o[1] for o in objs)
+                assert len({o[2] for o in objs}) == len(objs)
+                count, _ = K.class_counts(objs)
+                assert count[cls] and not any(count[c] for c in K.RAGGED if c != cls)
+                launched |= {c for c in range(K.FULL + 1) if count[c]}
+            n = K.wave_objects(cls, knob)
+            assert len(K.shared_wave(cls, knob)[0]) == (n + 3 if K.knob_lanes(cls, knob)[0] < 64 else 5)
+        assert launched == set(range(K.FULL + 1)), knob
+    objs, total = K.all_classes()
+    assert K.object_bytes(objs) <= K.BUDGET and all(K.class_counts(objs)[0])
+    for zeros in (True, False):
+        objs, total = K.many_tiny(20000, zeros)
+        assert len(objs) == 20000 and total < 3 << 20 and K.object_bytes(objs) <= K.BUDGET
+        assert {o[4] for o in objs} == ({1, 2} if zeros else {1})
+        assert [len(K.many_tiny(n, zeros)[0]) for n in (6500, 3)] == [6500, 3]
+
+
+def test_class_lengths_hold_every_delta():
+    """No list dropped a delta to meet the budget: around the last boundary it
+    kept, every b + delta inside the class is a tail of the list."""
+    import dgen_batch_cases as K
+    for knob in K.KNOBS:
+        for cls in K.RAGGED:
+            objs, _ = K.class_lengths(cls, knob)
+            tails = {o[1] % K.MIB for o in objs}
+            C, lo = K.class_ceiling(cls), (0 if cls == 0 else K.class_ceiling(cls) // 2)
+            b = K.boundaries(cls, knob)[-1]
+            assert {b + d for d in K.DELTAS if lo < b + d <= min(C, K.MIB - 1)} <= tails, (cls, knob)
+            assert {lo + 1, C - 1, min(C, K.MIB - 1)} <= tails

@@ -27,6 +27,8 @@ import threading
 import numpy as np
 import pytest
 
+from dgen_batch_cases import layout   # moved there unchanged: the CPU suite builds lists with it too
+
 pytestmark = pytest.mark.gpu
 
 MIB = 1 << 20
@@ -73,21 +75,6 @@ def dgen(S, oracle):
         a.setflags(write=False)
         return a
     return f
-
-
-def layout(sizes, params, seed0, rng):
-    """(off, size, seed, dedup, compress) per size: offsets that are multiples
-    of 16 and not of 4096, gaps of 16 to 4112 bytes, a seed per object;
-    params(k) -> (dedup, compress).  Returns (objects, buffer bytes)."""
-    objs, end = [], 0
-    for k, size in enumerate(sizes):
-        off = (end + 15) // 16 * 16 + 16 * rng.randint(1, 257)
-        if off % 4096 == 0:
-            off += 16
-        dd, comp = params(k)
-        objs.append((off, size, seed0 + 1000003 * k, dd, comp))
-        end = max(end, off + size)
-    return objs, (end + 15) // 16 * 16 + 4112
 
 
 def edge_objects(params, seed0=0x5EED, extra=()):
