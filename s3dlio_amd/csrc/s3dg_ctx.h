@@ -105,22 +105,8 @@ constexpr int kDefaultStoreStream = kStoreNTSC1, kDefaultStoreBatch = kStoreSC1;
 // (tools/batch_lab.py, profiles/r02/diag/batch_lab_store_*: 20 KiB+5 objects 4766 -> 6092 GB/s,
 // dense 32 KiB 5977 -> 6663, dense 64 KiB 5992 -> 6472; tiled layouts keep sc1)
 constexpr int kDefaultStoreDense = kStoreNTSC1;
-// Draws per lane (npz keystream, DG1).  Since the jump's state sequence runs
-// on the scalar unit (k_keystream), longer lanes win: 2048 draws per lane
-// (K2 8 GiB launches 6096 -> 6621 GB/s, 80 GiB 6436 -> 6596; DG1 c1 6141 ->
-// 6604 / 6434 -> 6621; profiles/r02/diag/ks/ks_draws_sweep.log), and K2
-// launches of at least kKsLongRounds rounds of resident waves take 4096
-// (80 GiB: 6718; with 1-wave workgroups in XCD groups also 8 GiB launches,
-// profiles/r02/diag/ks/ks_draws_new_shape.log).  DG1 stays at 2048:
-// at 4096 a wave would span two 1 MiB blocks and lose the scalar jump.
-constexpr uint64_t kDefaultKsMinDraws[2] = {2048, 2048};
-constexpr uint64_t kKsLongDraws = 4096;
-constexpr uint64_t kKsLongRounds = 4;   // 1-wave workgroups: 8 GiB launches (4 rounds) 6755 -> 6986 GB/s at 4096
-constexpr uint64_t kKsMinSpan = 256;          // fewest draws per lane for small launches
-// DG1 with a zero prefix (compress > 1): 512 draws per lane by default, so the
-// waves that skip the PRNG cover more of each block's prefix (d1 c2: 6413 ->
-// 6694 GB/s; at c1 the extra jumps cost: 5896 -> 5347, profiles/r02/diag/k2_xcd.log)
-constexpr uint64_t kDgenPrefixMinDraws = 512;
+// Draws per lane (kDefaultKsMinDraws, kKsLongDraws, kKsLongRounds, kKsMinSpan,
+// kDgenPrefixMinDraws): s3dg_ks_plan.h, with the rule and the measurements.
 // measured on MI355X (tools/k2_lab.py, profiles/r02/diag/k2_lab_r2e.log):
 // 512-B row pieces, 4-wave workgroups, 1024 draws per lane and sc1 stores for
 // both modes (K2 6010 vs 5803 GB/s at 2048 draws; DG1 c1 5933 / c2 6158 vs

@@ -10,6 +10,7 @@
 #include "s3dg_batch_plan.h"   // kBlk, the batch tile-shift range
 #include "s3dg_verify_batch_plan.h"
 #include "s3dg_dgen_batch_plan.h"   // DgenChunkRec, the batch's lane limits
+#include "s3dg_ks_plan.h"           // the uniform keystream launches' plan, fastmod
 
 // Sets the calling thread's error text (s3dg_last_error) and returns code.
 extern "C" int s3dg_internal_fail(int code, const char *msg);
@@ -33,10 +34,6 @@ struct PrefixParams {
     uint64_t m_unique;   // Lemire fastmod constants: floor(2^64 / d) + 1
     uint64_t m_fden;
 };
-
-// a % d for 32-bit a and d >= 1 with M = fastmod_magic(d) (Lemire, Kaser &
-// Kurz 2019, "Faster remainder by direct computation"); exact for all a, d < 2^32.
-inline uint64_t fastmod_magic(uint32_t d) { return ~0ull / d + 1; }
 
 // Batch sub-batches reach the device as the caller's 40-B descriptors
 // (empty objects dropped); the record ranges are derived there:

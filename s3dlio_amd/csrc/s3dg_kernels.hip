@@ -114,10 +114,7 @@ __device__ __forceinline__ void store16(uint8_t *p, u32x4 v) {
     else *reinterpret_cast<u32x4 *>(p) = v;
 }
 
-__device__ __forceinline__ uint32_t fastmod(uint32_t a, uint64_t M, uint32_t d) {
-    const uint64_t low = M * a;
-    return (uint32_t)__umul64hi(low, (uint64_t)d);
-}
+// fastmod: s3dg_ks_plan.h
 
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {   // SplitMix64 output function
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -887,21 +884,9 @@ __device__ __forceinline__ void xo_step(uint64_t &s0, uint64_t &s1, uint64_t &s2
     s0 = n0; s1 = n1; s2 = n2;
 }
 
-// Workgroups are dealt round-robin to the 8 XCDs, so consecutive ones write
-// through different L2s.  Each full group of 8*xg workgroups is remapped so
-// the xg workgroups one XCD receives take xg adjacent work units: every XCD
-// writes runs of xg*W*64 adjacent lane regions (the last,
-// partial group keeps the dealing order).  b: the workgroup's index in the
-// static grid of A.nwg workgroups (dealt to XCD b mod 8).
+// The XCD remap of a launch's workgroup b (s3dg_ks_plan.h).
 __device__ __forceinline__ uint64_t ks_remap(const KeystreamArgs &A, uint64_t b) {
-    if (A.xg > 1) {
-        const uint32_t gs = (uint32_t)__builtin_ctz(A.xg);
-        if (((b >> (gs + 3)) + 1) << (gs + 3) <= A.nwg) {
-            const uint64_t x = b & 7, k = b >> 3;
-            return ((k >> gs) << (gs + 3)) + (x << gs) + (k & (A.xg - 1));
-        }
-    }
-    return b;
+    return s3dg::ks_remap(A.xg, A.nwg, b);
 }
 
 // A lane's header: where its chunk lies, how long it and its zero prefix are,
@@ -1000,8 +985,9 @@ __device__ __forceinline__ void ks_unit(uint8_t *dst, const KeystreamArgs &A, co
                    : 0;
     }
     const uint64_t d0 = A.z0 + (uint64_t)sub * span;                 // first draw index
-    const uint64_t rb = d0 * 8;                                      // lane region within chunk
-    const uint32_t rlen = (uint32_t)(clen > rb ? ((clen - rb) < (uint64_t)span * 8 ? (clen - rb) : (uint64_t)span * 8) : 0);
+    const KsRegion reg = ks_lane_region(clen, A.z0, span, sub);      // lane region within chunk
+    const uint64_t rb = reg.rb;
+    const uint32_t rlen = reg.rlen;
     const uint64_t tail_draw = clen >> 3;                            // draw index of a 1..7 B tail
     const bool tail_hi = (clen & 7) >= 1 && (clen & 7) <= 4;         // next_u32 = next_u64 >> 32
     // zero prefix of the chunk (dgen-contract compressibility); 0 for the npz fill
@@ -1349,21 +1335,21 @@ __device__ __forceinline__ bool ks_take(const KeystreamArgs &A, const KeystreamA
     for (uint32_t i = 0; i < 8; ++i) {
         const uint32_t v = (x + i) & 7;
         if (gone & (1u << v)) continue;
-        const uint64_t quota = (uint64_t)W * ((A.nwg + 7 - v) / 8);
-        const uint64_t quota2 = (uint64_t)W * ((A2.nwg + 7 - v) / 8);   // A2.nwg = 0: no second set
+        const uint64_t quota = ks_queue_quota(A.nwg, v, W);
+        const uint64_t quota2 = ks_queue_quota(A2.nwg, v, W);   // A2.nwg = 0: no second set
         uint64_t q = 0;
         if (l == 0) q = __hip_atomic_fetch_add(ctr + 16 * v, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         q = readlane64(q, 0);
         if (q < quota) {
-            b = 8 * (q / W) + v;
-            w = (uint32_t)(q % W);
+            b = ks_queue_wg(q, v, W);
+            w = ks_queue_wave(q, W);
             second = false;
             return true;
         }
         if (q - quota < quota2) {
             q -= quota;
-            b = 8 * (q / W) + v;
-            w = (uint32_t)(q % W);
+            b = ks_queue_wg(q, v, W);
+            w = ks_queue_wave(q, W);
             second = true;
             return true;
         }
@@ -1819,10 +1805,7 @@ hipError_t launch_fill_uniform_tiles_ablated(const LaunchCfg &lc, uint8_t *dst, 
 // (profiles/r04/k/lib_ab.log): the three gains kept (6421 / 6987 / 7052
 // against 6232 / 6646 / 6705), 4-round launches unchanged (persistent from
 // one round: DG1 4 GiB launches 6175 -> 6151, K2 8 GiB 6400 -> 6376).
-#ifndef S3DG_KS_PERSIST_ROUNDS
-#define S3DG_KS_PERSIST_ROUNDS 6
-#endif
-constexpr uint32_t kKsPersistRounds = S3DG_KS_PERSIST_ROUNDS;
+// (kKsPersistRounds / S3DG_KS_PERSIST_ROUNDS: s3dg_ks_plan.h, ks_persistent_grid)
 
 // Resident workgroups per CU of a keystream shape (cached: the occupancy
 // query is a host-side calculation, but a host call's latency budget is µs).
@@ -1847,16 +1830,14 @@ hipError_t launch_keystream(uint8_t *dst, const KeystreamArgs &A0, const uint64_
                            const KeystreamArgs *tail, const uint64_t *tail_jtab) {
     (void)hipGetLastError();
     const uint32_t lds = occupancy_lds(sh.wgs_per_cu, ks_static_lds(sh.draws, sh.waves));
-    const uint32_t xg = sh.xcd_waves > sh.waves ? (uint32_t)(sh.xcd_waves / sh.waves) : 1u;
     // static-grid workgroups of an argument set
     auto grid_of = [&](KeystreamArgs &X) -> uint64_t {
-        X.xg = xg;
-        const uint64_t waves = (X.nchunks * X.lpc + 63) / 64;
-        const uint64_t wgs = (waves + sh.waves - 1) / sh.waves;
-        X.nwg = (uint32_t)(wgs > 0x7FFFFFFFull ? 0x7FFFFFFFull : wgs);
+        const KsGrid G = ks_static_grid(X.nchunks, X.lpc, sh.waves, sh.xcd_waves);
+        X.xg = G.xg;
+        X.nwg = G.nwg;
         X.ctr = nullptr;
         X.par = 0;
-        return wgs;
+        return G.wgs;
     };
     KeystreamArgs A = A0, A2{};
     const uint64_t wgs = grid_of(A);
@@ -1872,10 +1853,11 @@ hipError_t launch_keystream(uint8_t *dst, const KeystreamArgs &A0, const uint64_
     // at least `rounds` rounds of resident waves (default: 1-wave workgroups
     // from kKsPersistRounds): a persistent grid over per-XCD queues
     // (k_keystream), one resident round of workgroups, a multiple of 8
-    const uint64_t rounds = persist_rounds < 0 ? (sh.waves == 1 ? kKsPersistRounds : 0) : (uint64_t)persist_rounds;
-    if (rounds > 0 && ctrs && ctrs->dev && cus > 0) {
-        const uint64_t cap = ((uint64_t)ks_resident_per_cu(sh, lds) * (uint64_t)cus) & ~7ull;
-        if (cap >= 8 && wgs + wgs2 >= rounds * cap) {
+    const bool may = persist_rounds < 0 ? sh.waves == 1 && kKsPersistRounds > 0 : persist_rounds > 0;
+    if (may && ctrs && ctrs->dev && cus > 0) {
+        const uint64_t cap = ks_persistent_grid(wgs, wgs2, persist_rounds, (uint64_t)ks_resident_per_cu(sh, lds),
+                                                (uint64_t)cus, sh.waves);
+        if (cap) {
             A.ctr = ctrs->dev;
             A.par = ctrs->par;
             grid = cap;

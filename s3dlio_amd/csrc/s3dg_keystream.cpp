@@ -37,34 +37,14 @@ int s3dg::jump_table(s3dg_ctx *c, uint32_t lpc, uint64_t span, uint64_t z0, cons
 // tails of a DG1 zero-prefix split), one wave per tail when it has >= 64 x 256 draws.
 static int keystream_plan(s3dg_ctx *c, int mode, uint64_t chunk_bytes, uint64_t nchunks, bool zero_prefix,
                           KeystreamArgs &A, const uint64_t **jtab, uint64_t z0 = 0) {
-    const uint64_t nd = chunk_bytes / 8 - z0;
-    // as many lanes per chunk as keep >= ks_min_draws draws per lane (the
-    // jump costs 256 steps); up to 1024 lanes = 16 waves per chunk
-    uint64_t min_draws = c->ks_min_draws[mode];
-    if (mode == 1 && zero_prefix && min_draws == kDefaultKsMinDraws[1]) min_draws = kDgenPrefixMinDraws;
-    if (mode == 0 && min_draws == kDefaultKsMinDraws[0] && nd >= 64 * kKsLongDraws) {
-        // waves at 4096 draws per lane vs the chip's resident keystream waves
-        // (4 per CU: 64-draw stages take 33 KiB of LDS per wave)
-        const uint64_t waves = nchunks * (nd / kKsLongDraws) / 64;
-        if (waves >= kKsLongRounds * (uint64_t)c->cus * 4) min_draws = kKsLongDraws;
-    }
-    uint32_t lpc = 1;
-    while (lpc < 1024 && nd / (2 * lpc) >= min_draws) lpc *= 2;
-    // a tail: 64 lanes (one wave, the jump's state sequence on the scalar unit)
-    if (z0 && lpc < 64 && nd >= 64 * kKsMinSpan) lpc = 64;
-    // small launches (a few chunks): spread each chunk over more lanes, down
-    // to 256 draws per lane, until the grid has ~4 waves per CU; otherwise a
-    // 8 MiB request runs as 16 long waves and is latency-bound
-    const uint64_t target_lanes = (uint64_t)c->cus * 4 * 64;
-    while (lpc < 1024 && nchunks * lpc < target_lanes && nd / (2 * lpc) >= kKsMinSpan) lpc *= 2;
-    uint64_t span = (nd + lpc - 1) / lpc;
-    const uint64_t D = (uint64_t)c->ks[mode].draws;    // a lane stages D draws per iteration
-    span = (span + D - 1) / D * D;
-    if (span > 0xFFFFFFFFull) return fail(S3DG_EINVAL, "chunk too large");
-    A.lpc = lpc;
-    A.span = (uint32_t)span;
+    // the rules: ks_lanes (s3dg_ks_plan.h); a lane stages ks[mode].draws draws per iteration
+    const KsLanes L = ks_lanes(mode, chunk_bytes, nchunks, zero_prefix, z0, c->ks_min_draws[mode],
+                               (uint64_t)c->ks[mode].draws, (uint64_t)c->cus);
+    if (!L.ok) return fail(S3DG_EINVAL, "chunk too large");
+    A.lpc = L.lpc;
+    A.span = (uint32_t)L.span;
     A.z0 = z0;
-    return jump_table(c, lpc, span, z0, jtab);
+    return jump_table(c, L.lpc, L.span, z0, jtab);
 }
 
 // The stream's queue counters for persistent keystream launches, allocated
@@ -216,25 +196,24 @@ int half_tail_set(s3dg_ctx *c, const KsShape &sh, uint64_t n_objs, uint64_t nchu
         std::lock_guard<std::mutex> g(c->mu);
         tail_chunks = c->ks_tail;
     }
+    int res = 0;
     if (tail_chunks < 0) {
-        int res = 0;
         if (keystream_occupancy(sh, &res) != hipSuccess) res = 0;
         (void)hipGetLastError();
-        tail_chunks = (int64_t)((uint64_t)res * (uint64_t)c->cus * (uint64_t)sh.waves * 64 / A.lpc / 2);
     }
-    const uint32_t span2 = A.span / 2;
-    if (n_objs == 1 && tail_chunks > 0 && sh.waves == 1 && A.lpc >= 64 && A.lpc <= 512 && span2 >= kKsMinSpan &&
-        span2 % (uint32_t)sh.draws == 0 && nchunks >= 8 * (uint64_t)tail_chunks) {
-        const uint64_t T = (uint64_t)tail_chunks;
+    // the conditions and both sets' chunks: ks_half_tail (s3dg_ks_plan.h)
+    const KsHalfTail H = ks_half_tail(tail_chunks, (uint64_t)res, (uint64_t)c->cus, (uint32_t)sh.waves,
+                                      (uint32_t)sh.draws, n_objs, nchunks, A.chunk0, A.lpc, A.span);
+    if (H.take) {
         A2 = A;
-        A2.lpc = 2 * A.lpc;
-        A2.span = span2;
-        A2.nchunks = T;
-        A2.cpo = T;
-        A2.chunk0 = A.chunk0 + (nchunks - T);
-        A2.doff = (nchunks - T) * kDgenBlock;
-        A.nchunks = nchunks - T;
-        A.cpo = nchunks - T;
+        A2.lpc = H.lpc2;
+        A2.span = H.span2;
+        A2.nchunks = H.T;
+        A2.cpo = H.cpo2;
+        A2.chunk0 = H.chunk0_2;
+        A2.doff = H.doff;
+        A.nchunks = H.nchunks1;
+        A.cpo = H.cpo1;
         if (int r = jump_table(c, A2.lpc, A2.span, A2.z0, jt2)) return r;
         *tail = true;
     }
@@ -262,11 +241,11 @@ int dgen_chunk(s3dg_ctx *c, void *dst, uint64_t obj_size, uint64_t stride, uint6
     // of the prefix (< 4 KiB) in its lane rows.  Tails that start inside a
     // granule (zw down to 16 B) ran 25-35 % slower: lane regions off the
     // 128-B lines (profiles/r05/g).
-    const uint64_t nchunks = (blk_hi - blk_lo) * n_objs;
-    const uint32_t zw = (uint32_t)(kDgenBlock * f_num / f_den) & ~(kBlk - 1);
-    const bool ragged_end = obj_size % kDgenBlock != 0 && blk_hi == nb;
-    if (f_num > 0 && Z.split && ragged_end && blk_hi - 1 > blk_lo && (blk_hi - 1 - blk_lo) * n_objs >= Z.split &&
-        zw >= 8 * kBlk) {
+    // The decisions: ks_dgen_call (s3dg_ks_plan.h).
+    const KsDgenCall P = ks_dgen_call(obj_size, n_objs, blk_lo, blk_hi, f_num, f_den, Z.split);
+    const uint64_t nchunks = P.nchunks;
+    const uint32_t zw = P.zw;
+    if (P.cut_last) {
         // the objects' full blocks split, their short last blocks in a launch of their own
         if (int r = dgen_chunk(c, dst, obj_size, stride, n_objs, blk_lo, blk_hi - 1, dedup, f_num, f_den, seed_base,
                                first_obj, stream))
@@ -274,10 +253,10 @@ int dgen_chunk(s3dg_ctx *c, void *dst, uint64_t obj_size, uint64_t stride, uint6
         return dgen_chunk(c, (uint8_t *)dst + (blk_hi - 1 - blk_lo) * kDgenBlock, obj_size, stride, n_objs, blk_hi - 1,
                           blk_hi, dedup, f_num, f_den, seed_base, first_obj, stream);
     }
-    const bool zsplit = f_num > 0 && Z.split && nchunks >= Z.split && zw >= 8 * kBlk && !ragged_end;
+    const bool zsplit = P.zsplit;
     KeystreamArgs A{};
     const uint64_t *jt = nullptr;
-    if (int r = keystream_plan(c, 1, kDgenBlock, nchunks, f_num > 0 && !zsplit, A, &jt, zsplit ? zw / 8 : 0))
+    if (int r = keystream_plan(c, 1, kDgenBlock, nchunks, f_num > 0 && !zsplit, A, &jt, P.z0))
         return r;
     const uint64_t U = s3dg_unique_blocks(nb, dedup);
     A.cpo = blk_hi - blk_lo;
