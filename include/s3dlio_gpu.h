@@ -733,6 +733,36 @@ int s3dg_device_count(int *out);
 /* ---- CRC-32 and NPZ (src/data_formats/npz.rs:322-434) --------------------- */
 /* CRC-32 (IEEE, crc32fast / zlib.crc32) of dev[0, len); synchronous on `stream`. */
 int s3dg_crc32(s3dg_ctx *ctx, const void *dev, uint64_t len, void *stream, uint32_t *out);
+/* The CRC-32 of every object of a mixed-size batch in one call (DESIGN.md
+ * §5.4.1): crcs[k] is s3dg_crc32's value for the size_k bytes at
+ * src_base + off_k, the checksum every writer hands back with its object; an
+ * empty span gives 0, whatever its off.  Regions, tails and the fold of an
+ * object's regions all run on the device: one launch over the regions of all
+ * objects, one over the objects.
+ * Layout (as s3dg_measure_add_batch): spans may come in any order, leave gaps,
+ * overlap and repeat; a repeated span gives the same value twice.  off of a
+ * non-empty span is a multiple of 16, size anything up to 2^31 x 4096.
+ * Reading: a 16-byte piece is loaded whole only when it ends at or below its
+ * object's end, the ragged piece byte by byte; no byte of a gap is ever read,
+ * nor any byte before src_base + off or at or past off + size.  Nothing is
+ * written to the payload.
+ * s3dg_crc32_batch_async is ordered on `stream` and returns without waiting:
+ * `spans` is consumed before it returns, crcs_dev is device memory or pinned
+ * host memory of n values, all of which are written in stream order (those of
+ * empty spans as zeros); there is no copy back and no wait in it.
+ * s3dg_crc32_batch is that into scratch of the stream's, one copy of 4 n bytes
+ * into the host array crcs and one wait.  The table of a call (32 bytes per
+ * non-empty span, 24 per region of 32 KiB or more) and its scratch belong to
+ * the stream: calls on different streams of one context share nothing that
+ * changes, so threads on different streams need no lock of their own.
+ * Refusals (S3DG_EINVAL; every span is checked before anything is reserved or
+ * enqueued, so a refused call has read nothing and written nothing to crcs):
+ * "null context", "null output", and s3dg_measure_add_batch's for the spans,
+ * with its messages.  n == 0 succeeds whatever the other pointers. */
+int s3dg_crc32_batch(s3dg_ctx *ctx, const void *src_base, const s3dg_span *spans, uint64_t n, void *stream,
+                     uint32_t *crcs);
+int s3dg_crc32_batch_async(s3dg_ctx *ctx, const void *src_base, const s3dg_span *spans, uint64_t n, void *stream,
+                           uint32_t *crcs_dev);
 /* zlib crc32_combine: CRC of A||B from crc(A), crc(B), |B| (host). */
 uint32_t s3dg_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2);
 /* Host CRC-32 update (crc32fast::Hasher semantics: start from 0). */

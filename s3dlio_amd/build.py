@@ -29,7 +29,7 @@ SOURCES = [os.path.join(CSRC, "s3dg_kernels.hip"), os.path.join(CSRC, "s3dg_capi
            os.path.join(CSRC, "s3dg_measure.cpp"), os.path.join(CSRC, "s3dg_chunks.hip"),
            os.path.join(CSRC, "s3dg_chunks.cpp"), os.path.join(CSRC, "s3dg_lz.hip"),
            os.path.join(CSRC, "s3dg_lz.cpp"), os.path.join(CSRC, "s3dg_verify_batch.cpp"),
-           os.path.join(CSRC, "s3dg_dgen_batch.cpp")]
+           os.path.join(CSRC, "s3dg_dgen_batch.cpp"), os.path.join(CSRC, "s3dg_crc_batch.cpp")]
 HEADERS = [os.path.join(CSRC, "s3dg_internal.h"), os.path.join(CSRC, "s3dg_ctx.h"),
            os.path.join(CSRC, "s3dg_batch_plan.h"), os.path.join(CSRC, "s3dg_ks_verify_plan.h"),
            os.path.join(CSRC, "s3dg_jump.h"), os.path.join(CSRC, "s3dg_measure_plan.h"),
@@ -39,7 +39,7 @@ HEADERS = [os.path.join(CSRC, "s3dg_internal.h"), os.path.join(CSRC, "s3dg_ctx.h
            os.path.join(CSRC, "s3dg_verify_batch_plan.h"), os.path.join(CSRC, "s3dg_span_plan.h"),
            os.path.join(CSRC, "s3dg_span_batch_plan.h"),
            os.path.join(CSRC, "s3dg_accum.h"), os.path.join(CSRC, "s3dg_dgen_batch_plan.h"),
-           os.path.join(CSRC, "s3dg_ks_plan.h"),
+           os.path.join(CSRC, "s3dg_ks_plan.h"), os.path.join(CSRC, "s3dg_crc_batch_plan.h"),
            os.path.join(ROOT, "include", "s3dlio_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

@@ -123,6 +123,12 @@ void stream_state_free(StreamState *S) {
         if (T.dev) (void)hipFree(T.dev);
         if (T.uploaded) (void)hipEventDestroy(T.uploaded);
     }
+    for (auto &T : S->ctab) {
+        if (T.host) (void)hipHostFree(T.host);
+        if (T.dev) (void)hipFree(T.dev);
+        if (T.uploaded) (void)hipEventDestroy(T.uploaded);
+    }
+    if (S->crc_out) (void)hipFree(S->crc_out);
     delete S;
 }
 

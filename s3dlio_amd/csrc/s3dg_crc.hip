@@ -9,7 +9,10 @@
 // Kernel: one wave per contiguous region (256 KiB by default), column-Horner
 // (k_crc32_regions); the host folds the region CRCs (table-driven constant
 // multiply) and hashes the sub-region tail itself.  Reads only: HBM-read bound.
+// A mixed-size batch (s3dg_crc32_batch) runs regions, tails and fold on the
+// device: k_crc32_batch_regions and k_crc32_batch_fold, below the two above.
 #include "s3dg_internal.h"
+#include "s3dg_crc_batch_plan.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -254,6 +257,131 @@ __global__ __launch_bounds__(512) void k_crc32_regions_cf(CrcSegArgs a, const Cr
     }
 }
 
+// ---- a mixed-size batch (s3dg_crc32_batch) -------------------
+// One wave per region record of s3dg_crc_batch_plan.h, in k_crc32_regions_cf's
+// shape: 8-wave workgroups, the single-bank tables in LDS, the grid sized to
+// the chip, each wave looping over records.  The row step (the rotated
+// schedule, the Horner sum, two register buffers of four rows) is that
+// kernel's, restated here so that its code stays exactly what the NPZ builder
+// and the PUT pipeline were measured with.  New: the region's tail of
+// t = 16 j + e < 1024 bytes is hashed by the same wave.  With W the rows' raw
+// CRC spread over the lanes (XOR_l V_l) and piece l the tail's bytes
+// [16 l, 16 l + 16),
+//   raw = A^e ( A^(16 j) W  ^  XOR_{l < j} A^(16 (j - 1 - l)) raw16(piece l) )  ^  raw(last e bytes),
+// where A^(16 k) is lane_shift[63 - k] and A^e is byte_shift[e].  Lane l < j
+// loads piece l whole (it ends at or below the object's end), lane j reads the
+// last e bytes one by one; nothing else of the tail's row is touched.
+__global__ __launch_bounds__(512) void k_crc32_batch_regions(const uint8_t *src, const CrcBatchRec *recs, uint64_t nrec,
+                                                             const CrcTablesCF *tabs, const uint32_t *lane_shift,
+                                                             const uint32_t *byte_shift, uint32_t *raw) {
+    __shared__ CrcTablesCF T;
+    const uint32_t t = threadIdx.x, lane = t & 63;
+    {
+        const uint4 *g = reinterpret_cast<const uint4 *>(tabs);
+        uint4 *d = reinterpret_cast<uint4 *>(&T);
+        for (uint32_t k = t; k < sizeof(CrcTablesCF) / 16; k += 512) d[k] = g[k];
+    }
+    __syncthreads();
+    const uint32_t s = (lane >> 2) & 3, cb = (lane >> 4) & 1, cr = (lane >> 2) & 7;
+    uint32_t offb[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const uint32_t b = 4 * (((uint32_t)(q >> 2) + s) & 3) + (((uint32_t)q + lane) & 3);
+        offb[q] = 4 * (2 * (15 - b) + cb);
+    }
+    uint32_t shb[4], offr[4], shr[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        shb[m] = 8 * (((uint32_t)m + lane) & 3);
+        const uint32_t tt = ((uint32_t)m + lane) & 3;
+        shr[m] = 8 * tt;
+        offr[m] = 4 * (8 * tt + cr);
+    }
+    const bool rot2 = s & 2, rot1 = s & 1;
+    const uint8_t *tb = reinterpret_cast<const uint8_t *>(T.tb);
+    const uint8_t *tr = reinterpret_cast<const uint8_t *>(T.tr);
+    auto look = [&](const uint8_t *base, uint32_t byte, uint32_t off) -> uint32_t {
+        return *reinterpret_cast<const uint32_t *>(base + (byte << 7) + off);
+    };
+    auto row = [&](uint32_t S, const uint4 v) -> uint32_t {
+        const uint32_t x0 = rot2 ? v.z : v.x, x1 = rot2 ? v.w : v.y, x2 = rot2 ? v.x : v.z, x3 = rot2 ? v.y : v.w;
+        const uint32_t w[4] = {rot1 ? x1 : x0, rot1 ? x2 : x1, rot1 ? x3 : x2, rot1 ? x0 : x3};
+        uint32_t u[20];
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            u[q] = look(tb, __builtin_amdgcn_ubfe(w[q >> 2], shb[q & 3], 8), offb[q]);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) u[16 + m] = look(tr, __builtin_amdgcn_ubfe(S, shr[m], 8), offr[m]);
+        const uint32_t a0 = xor3(u[0], u[1], u[2]), a1 = xor3(u[3], u[4], u[5]), a2 = xor3(u[6], u[7], u[8]);
+        const uint32_t a3 = xor3(u[9], u[10], u[11]), a4 = xor3(u[12], u[13], u[14]);
+        const uint32_t a5 = xor3(u[15], u[16], u[17]), a6 = u[18] ^ u[19];
+        return xor3(xor3(a0, a1, a2), xor3(a3, a4, a5), a6);
+    };
+    const uint64_t nwaves = (uint64_t)gridDim.x * 8;
+    for (uint64_t r = (uint64_t)blockIdx.x * 8 + (t >> 6); r < nrec; r += nwaves) {
+        const CrcBatchRec R = recs[r];
+        const uint32_t nrows = R.rows;
+        const uint8_t *base = src + R.off;
+        const uint4 *p = reinterpret_cast<const uint4 *>(base) + lane;
+        uint32_t S = 0, rw = 0;
+        auto load4 = [&](uint4 (&v)[4], uint32_t r0) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t rr = r0 + q < nrows ? r0 + q : nrows - 1;
+                v[q] = p[(uint64_t)rr * 64];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        uint4 A[4], B[4];
+        if (nrows >= 4) load4(A, 0);
+        for (; rw + 8 <= nrows; rw += 8) {
+            load4(B, rw + 4);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) S = row(S, A[q]);
+            __builtin_amdgcn_sched_barrier(0);
+            load4(A, rw + 8);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) S = row(S, B[q]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (rw + 4 <= nrows) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) S = row(S, A[q]);
+            rw += 4;
+        }
+        for (; rw < nrows; ++rw) S = row(S, p[(uint64_t)rw * 64]);
+        S = multmodp(lane_shift[lane], S);              // A^(16 (63 - lane))
+        if (R.tail) {
+            const uint32_t j = R.tail >> 4, e = R.tail & 15;
+            const uint8_t *tp = base + (uint64_t)nrows * kCrcRowBytes;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (lane < j) v = reinterpret_cast<const uint4 *>(tp)[lane];
+            const uint32_t piece = row(0, v);                       // raw16: the row tables give 0 for S = 0
+            const uint32_t behind = lane < j ? j - 1 - lane : 0;    // whole pieces after this lane's
+            S = multmodp(lane_shift[63 - j], S) ^ multmodp(lane_shift[63 - behind], piece);
+            S = multmodp(byte_shift[e], S);
+            if (lane == j && e) {
+                uint32_t c = 0;
+                for (uint32_t q = 0; q < e; ++q) c = (c >> 8) ^ T.tb[((c ^ tp[16 * j + q]) & 0xFF) * 32];   // tbyte[0]
+                S ^= c;
+            }
+        }
+#pragma unroll
+        for (int q = 32; q >= 1; q >>= 1) S ^= __shfl_xor(S, q);
+        if (lane == 0) raw[r] = S;
+    }
+}
+
+// One thread per entry: the plan header's fold over the object's raws, the
+// powers of x it needs computed here, the CRC-32 stored at the caller's index.
+__global__ __launch_bounds__(256) void k_crc32_batch_fold(const CrcBatchEnt *ents, uint64_t live, const uint32_t *raw,
+                                                          uint32_t *crcs) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= live) return;
+    const CrcBatchEnt E = ents[i];
+    crcs[E.k] = crcb_fold(raw + E.reg0, E.nreg, E.rows, E.size);
+}
+
 // x^(8 n) mod P (zlib x2nmodp(n, 3)) on the host.
 uint32_t x8n(uint64_t n) {
     uint32_t p = 1u << 31;           // x^0
@@ -268,11 +396,14 @@ uint32_t x8n(uint64_t n) {
     return p;
 }
 
+constexpr size_t kByteShiftOff = sizeof(CrcTables) + 64 * 4 + sizeof(CrcTablesCF);
+
 uint32_t crc_tables[8][256];
 bool tables_ready = false;
 CrcTables dev_tables_host;
 CrcTablesCF dev_tables_cf_host;
 uint32_t lane_shift_host[64];
+uint32_t byte_shift_host[16];   // x^(8 e), e = 0..15: the multipliers A^e of k_crc32_batch_regions' tails
 
 void init_tables() {
     if (tables_ready) return;
@@ -296,6 +427,7 @@ void init_tables() {
     for (int b = 0; b < 4; ++b)
         for (uint32_t x = 0; x < 256; ++x) dev_tables_host.trow[b][x] = multmodp(x1k, x << (8 * b));
     for (int l = 0; l < 64; ++l) lane_shift_host[l] = x8n(16ull * (63 - l));
+    for (int e = 0; e < 16; ++e) byte_shift_host[e] = x8n((uint64_t)e);
     for (uint32_t i = 0; i < 256; ++i) {
         for (int t = 0; t < 16; ++t)
             for (int c = 0; c < 2; ++c) dev_tables_cf_host.tb[i * 32 + 2 * t + c] = dev_tables_host.tbyte[t][i];
@@ -340,8 +472,11 @@ hipError_t crc_tables_device(void **tab_cache) {
     }
     if (*tab_cache) return hipSuccess;
     hipError_t e;
-    // [CrcTables][lane shifts, 256 B][CrcTablesCF]
-    if ((e = hipMalloc(tab_cache, sizeof(CrcTables) + 64 * 4 + sizeof(CrcTablesCF))) != hipSuccess) return e;
+    // [CrcTables][lane shifts, 256 B][CrcTablesCF][byte shifts, 64 B]
+    if ((e = hipMalloc(tab_cache, kByteShiftOff + 16 * 4)) != hipSuccess) return e;
+    if ((e = hipMemcpy((uint8_t *)*tab_cache + kByteShiftOff, byte_shift_host, 16 * 4, hipMemcpyHostToDevice)) !=
+        hipSuccess)
+        return e;
     if ((e = hipMemcpy(*tab_cache, &dev_tables_host, sizeof(CrcTables), hipMemcpyHostToDevice)) != hipSuccess)
         return e;
     if ((e = hipMemcpy((uint8_t *)*tab_cache + sizeof(CrcTables), lane_shift_host, 64 * 4,
@@ -404,6 +539,26 @@ hipError_t crc_seg_launch(const CrcSegPlan &P, const uint8_t *dev, void *tab_dev
         hipLaunchKernelGGL(k_crc32_regions, dim3((uint32_t)wgs), dim3(256), 0, s, a, (const CrcTables *)tab_dev, lsh,
                            out_dev);
     }
+    return hipGetLastError();
+}
+
+hipError_t crc_batch_launch(const uint8_t *src_base, const uint8_t *table_dev, const CrcBatchCounts &C, void *tab_dev,
+                            int cus, uint32_t *crcs_dev, hipStream_t s) {
+    if (C.live == 0) return hipSuccess;
+    const CrcBatchEnt *ents = reinterpret_cast<const CrcBatchEnt *>(table_dev);
+    const CrcBatchRec *recs = reinterpret_cast<const CrcBatchRec *>(table_dev + crc_batch_rec_offset(C.live));
+    uint32_t *raw = reinterpret_cast<uint32_t *>(const_cast<uint8_t *>(table_dev) + crc_batch_raw_offset(C));
+    const uint8_t *tab = (const uint8_t *)tab_dev;
+    // 8-wave workgroups of 64 KiB LDS: two per CU, every wave looping over records
+    const uint64_t need = (C.regions + 7) / 8, fit = 2ull * (uint64_t)(cus > 0 ? cus : 256);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_crc32_batch_regions, dim3((uint32_t)(need < fit ? need : fit)), dim3(512), 0, s, src_base, recs,
+                       C.regions, (const CrcTablesCF *)(tab + sizeof(CrcTables) + 64 * 4),
+                       (const uint32_t *)(tab + sizeof(CrcTables)), (const uint32_t *)(tab + kByteShiftOff), raw);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_crc32_batch_fold, dim3((uint32_t)((C.live + 255) / 256)), dim3(256), 0, s, ents, C.live,
+                       (const uint32_t *)raw, crcs_dev);
     return hipGetLastError();
 }
 

@@ -2,7 +2,7 @@
 // state and the measured defaults.  Private to the units that implement
 // include/s3dlio_gpu.h over the context (s3dg_capi.cpp, s3dg_tune.cpp,
 // s3dg_fill.cpp, s3dg_batchfill.cpp, s3dg_verify_batch.cpp, s3dg_keystream.cpp,
-// s3dg_dgen_batch.cpp,
+// s3dg_dgen_batch.cpp, s3dg_crc_batch.cpp,
 // and, through s3dg_accum.h, s3dg_measure.cpp, s3dg_chunks.cpp and
 // s3dg_lz.cpp); everything else
 // reaches a context through the functions of s3dg_internal.h.
@@ -188,6 +188,18 @@ struct StreamState {
         hipEvent_t uploaded = nullptr;
     } dtab[2];
     int dnext = 0;
+    // tables of batch CRC calls (s3dg_crc_batch.cpp), kept as the DG1 batch
+    // keeps its records: two sets, the pinned side free once `uploaded`, the
+    // device side ([entries | records | raw CRCs]) ordered by the stream; and
+    // the result scratch of the synchronous form, which drains the stream
+    struct CrcTable {
+        uint8_t *host = nullptr, *dev = nullptr;
+        uint64_t host_cap = 0, dev_cap = 0;
+        hipEvent_t uploaded = nullptr;
+    } ctab[2];
+    int cnext = 0;
+    uint32_t *crc_out = nullptr;
+    uint64_t crc_out_cap = 0;
     // lifetime (under the context's mu): users holding the state, and whether
     // s3dg_stream_release has taken it out of the context's map; the last
     // holder of a released state drains the stream and frees it

@@ -11,6 +11,7 @@
 #include "s3dg_verify_batch_plan.h"
 #include "s3dg_dgen_batch_plan.h"   // DgenChunkRec, the batch's lane limits
 #include "s3dg_ks_plan.h"           // the uniform keystream launches' plan, fastmod
+#include "s3dg_crc_batch_plan.h"    // CrcBatchCounts, the batch CRC's table
 
 // Sets the calling thread's error text (s3dg_last_error) and returns code.
 extern "C" int s3dg_internal_fail(int code, const char *msg);
@@ -375,6 +376,13 @@ hipError_t crc_seg_launch(const CrcSegPlan &P, const uint8_t *dev, void *tab_dev
                           hipStream_t s);
 void crc_seg_fold(const CrcSegPlan &P, const uint32_t *regions, const uint8_t *const *tails,
                   uint32_t *crcs);
+// A mixed-size batch (s3dg_crc32_batch; s3dg_crc_batch_plan.h): table_dev is
+// the uploaded [entries | records] with room for the regions' raw CRCs behind
+// it (crc_batch_device_bytes).  k_crc32_batch_regions hashes every region,
+// tails included, then k_crc32_batch_fold stores each entry's CRC-32 at
+// crcs_dev[its k] (device or pinned host memory).  Nothing for C.live == 0.
+hipError_t crc_batch_launch(const uint8_t *src_base, const uint8_t *table_dev, const CrcBatchCounts &C, void *tab_dev,
+                            int cus, uint32_t *crcs_dev, hipStream_t s);
 
 // ---- NUMA placement of host buffers (s3dg_numa.cpp) -------------------------
 bool device_local_cpus(int device, cpu_set_t *out);

@@ -773,6 +773,32 @@ class Context:
             m.add_batch(src, objects, stream=stream)
             return m.result()
 
+    # -- checksums of a mixed-size batch (read-only) --------------------------------
+    def crc32_batch(self, src, objects, stream=None, out=None):
+        """The CRC-32 (zlib.crc32) of every object of a mixed-size batch in one
+        call: objects is fill_batch's iterable, of which the first two fields
+        (off, size, ...) are used, or a uint64 numpy array of shape (n, 2), as
+        Measure.add_batch takes them.  Spans may come in any order, leave
+        gaps, overlap and repeat; an empty one gives 0.  off + size is checked
+        against `src`'s size before any launch (ValueError).  Returns a
+        numpy uint32 array of n values after waiting for them; with `out`, a
+        uint32 or int32 tensor of n elements on this context's device, the
+        values are stored there in stream order and the call returns None
+        without waiting."""
+        arr, n, need = _spans(objects)
+        p = self._src(src, need)
+        if out is None:
+            res = np.zeros(n, np.uint32)
+            call("s3dg_crc32_batch", self._h, p, arr, n, self._s(stream),
+                 res.ctypes.data_as(ctypes.POINTER(c_u32)))
+            return res
+        if not hasattr(out, "data_ptr") or str(out.dtype) not in ("torch.uint32", "torch.int32"):
+            raise ValueError("out must be a uint32 or int32 tensor")
+        if int(out.numel()) != n:
+            raise ValueError(f"out holds {int(out.numel())} elements, the batch has {n} objects")
+        call("s3dg_crc32_batch_async", self._h, p, arr, n, self._s(stream), self._dst(out, 4 * n))
+        return None
+
     def write_ceiling(self, dst, nbytes: int | None = None, pattern: int = 0xA5A5A5A5,
                       stream=None) -> None:
         n = _nbytes(dst) if nbytes is None else int(nbytes)
