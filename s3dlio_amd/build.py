@@ -40,6 +40,7 @@ HEADERS = [os.path.join(CSRC, "s3dg_internal.h"), os.path.join(CSRC, "s3dg_ctx.h
            os.path.join(CSRC, "s3dg_span_batch_plan.h"),
            os.path.join(CSRC, "s3dg_accum.h"), os.path.join(CSRC, "s3dg_dgen_batch_plan.h"),
            os.path.join(CSRC, "s3dg_ks_plan.h"), os.path.join(CSRC, "s3dg_crc_batch_plan.h"),
+           os.path.join(CSRC, "s3dg_prefix.h"),
            os.path.join(ROOT, "include", "s3dlio_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

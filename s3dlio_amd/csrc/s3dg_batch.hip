@@ -10,14 +10,12 @@ namespace s3dg {
 namespace {
 
 // tile records of one object: its blocks behind `lead` dead slots (its 4 KiB
-// granule mod 8, so every workgroup's slot = granule mod 8), rounded up to tiles
+// granule mod 8), rounded up to tiles: the record rules of s3dg_batch_plan.h
 struct TileCount {
     uint64_t base;
     uint32_t tshift;
     __host__ __device__ uint64_t operator()(const s3dg_obj_desc &o) const {
-        const uint64_t nb = (o.size + kBlk - 1) / kBlk;
-        const uint64_t lead = ((base + o.dst_off) >> 12) & 7;
-        return (nb + lead + (1ull << tshift) - 1) >> tshift;
+        return obj_tiles(obj_blocks(o.size), obj_lead(base, o.dst_off), tshift);
     }
 };
 

@@ -5,13 +5,20 @@
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "s3dlio_gpu.h"
 
 namespace s3dg {
 
 constexpr uint32_t kBlk = 4096;   // BLK_SIZE   src/constants.rs:326
 // batch tiles (tile -> object map granule) are 2^tshift blocks, tshift in
-// [kTileShiftMin, kTileShiftMax], chosen per launch (pick_tile_shift, plan_sub_batch)
+// [kTileShiftMin, kTileShiftMax], chosen per launch (pick_tile_shift, plan_sub_batch).
+// An object's records start at a multiple of its tile and its block 0 sits
+// `lead` slots in, so a slot equals the granule it writes modulo min(8, tile):
+// modulo 8 (each XCD writes its own granules) from 8-block tiles up and in the
+// dense layout, modulo 2 and 4 only for the forced 2- and 4-block tiles.
 constexpr uint32_t kTileShiftMin = 1, kTileShiftMax = 6;
 // the per-launch choice considers 8..64-block tiles only: 2- and 4-block tiles
 // (s3dg_set_batch_tile) cut dead slots but lose more to records, e.g. 16-B
@@ -19,6 +26,74 @@ constexpr uint32_t kTileShiftMin = 1, kTileShiftMax = 6;
 constexpr uint32_t kTileShiftAutoMin = 3;
 // tshift 0 (one record per 4 KiB granule of the batch's address range, no
 // per-object lead) is the dense layout for small packed objects
+
+// ---- the record rules ------------------------------------------------------------
+// What one object gets in a sub-batch's record map, as functions the host's
+// pass and the device's scan functor and k_batch_map share (S3DG_BP_HD), so a
+// CPU sweep walks the very arithmetic the kernels run
+// (tests/capi/batch_records_sweep.cpp).
+#if defined(__HIPCC__)
+#define S3DG_BP_HD __host__ __device__
+#else
+#define S3DG_BP_HD
+#endif
+
+S3DG_BP_HD inline uint64_t obj_blocks(uint64_t size) { return (size + kBlk - 1) / kBlk; }
+
+// Lead of an object: the 4 KiB granule (mod 8) of its first byte's address,
+// base + dst_off.  A tiled object's block 0 sits at slot `lead` of its first
+// tile, so slot and granule agree modulo the tile size (up to 8).
+S3DG_BP_HD inline uint64_t obj_lead(uint64_t base, uint64_t dst_off) { return ((base + dst_off) >> 12) & 7; }
+
+// Tiles (records) of nb blocks behind `lead` dead slots, rounded up.
+S3DG_BP_HD inline uint64_t obj_tiles(uint64_t nb, uint64_t lead, uint32_t tshift) {
+    return (nb + lead + (1ull << tshift) - 1) >> tshift;
+}
+
+// Records [lo, hi) of one object in its class's map and the slot of its block 0
+// behind lo << tshift.
+struct RecRange {
+    uint64_t lo, hi, lead;
+};
+
+// Tiled: `scan` = the exclusive sum of obj_tiles over the class's objects before it.
+S3DG_BP_HD inline RecRange tiled_records(uint64_t scan, uint64_t nb, uint64_t base, uint64_t dst_off, uint32_t tshift) {
+    const uint64_t lead = obj_lead(base, dst_off);
+    return RecRange{scan, scan + obj_tiles(nb, lead, tshift), lead};
+}
+
+// Dense: record = granule of the sub-batch's address range, counted from the
+// first object's granule (mod 8) lead0, so the object's block 0 is at slot g0 =
+// lead0 + (dst_off - first_off) / 4 KiB.  The first object's records start at
+// 0 (its lead is lead0); every other object's at g0.  They end at the
+// successor's g0 (has_next: next_off is its dst_off), so the gap behind an
+// object is its dead slots, or behind its last block.
+S3DG_BP_HD inline RecRange dense_records(bool is_first, uint64_t lead0, uint64_t first_off, uint64_t dst_off,
+                                         uint64_t nb, bool has_next, uint64_t next_off) {
+    const uint64_t g0 = lead0 + (dst_off - first_off) / kBlk;
+    const uint64_t lo = is_first ? 0 : g0;
+    return RecRange{lo, has_next ? lead0 + (next_off - first_off) / kBlk : g0 + nb, g0 - lo};
+}
+
+// Records of the dense layout of objects from first_off to last_end, the
+// first one at granule lead0 (mod 8).
+S3DG_BP_HD inline uint64_t dense_span(uint64_t lead0, uint64_t first_off, uint64_t last_end) {
+    return lead0 + (last_end - first_off) / kBlk;
+}
+
+// k_batch_map: an object of at most this many records writes them itself; the
+// records of one with more are written by its whole wave, 64 per pass.
+constexpr uint64_t kMapOwnRecords = 16;
+S3DG_BP_HD inline bool map_own_records(uint64_t recs) { return recs <= kMapOwnRecords; }
+
+// Slot k of the tile whose first slot is `first`: the object's block, negative
+// for a lead slot (dead, as a block at or past the object's end is).  Restates
+// k_fill_batch's expression `(int64_t)e.first + k - e.lead`, which stays written
+// out in the kernel.
+S3DG_BP_HD inline int64_t slot_block(uint32_t first, uint32_t k, uint32_t lead) { return (int64_t)first + k - lead; }
+
+// The small class of a split sub-batch (s3dg_set_batch_split).
+S3DG_BP_HD inline bool split_small(uint64_t nb, uint64_t split) { return nb < split; }
 
 // Launch classes by zero prefix (per launch; batches by majority of blocks)
 enum ZeroClass { kZcNone = 0, kZcLines = 1, kZcMidHeavy = 2 };
@@ -125,14 +200,14 @@ static inline void batch_scan(const s3dg_obj_desc *__restrict d, uint64_t k0, ui
         if (m == 0) ufirst = o;
         else uni = uni && uni_next(ufirst, uprev, o, ustride);
         uprev = o;
-        const uint64_t nb = (o.size + kBlk - 1) / kBlk;
+        const uint64_t nb = obj_blocks(o.size);
         bad |= (o.dst_off & 15u) != 0 || o.f_den == 0 || o.f_num >= o.f_den || nb >= (1ull << 31);
-        const uint64_t x = nb + (((base + o.dst_off) >> 12) & 7);   // blocks behind the XCD lead
-        for (uint32_t sh = kTileShiftMin; sh <= kTileShiftMax; ++sh) nt[sh] += (x + (1ull << sh) - 1) >> sh;
-        if (nb < split) {
+        const uint64_t lead = obj_lead(base, o.dst_off);   // the blocks sit behind the XCD lead
+        for (uint32_t sh = kTileShiftMin; sh <= kTileShiftMax; ++sh) nt[sh] += obj_tiles(nb, lead, sh);
+        if (split_small(nb, split)) {
             ++ms;
             blocks_s += nb;
-            for (uint32_t sh = kTileShiftMin; sh <= kTileShiftMax; ++sh) nts[sh] += (x + (1ull << sh) - 1) >> sh;
+            for (uint32_t sh = kTileShiftMin; sh <= kTileShiftMax; ++sh) nts[sh] += obj_tiles(nb, lead, sh);
         }
         if (m == 0) first = o.dst_off;
         dense = dense && (m == 0 || o.dst_off >= last) && (o.dst_off & (kBlk - 1)) == 0;
@@ -257,8 +332,8 @@ inline BatchPlan plan_sub_batch(const BatchScan &P, uintptr_t base, const BatchK
         B.uniform = true;
         return B;
     }
-    B.lead0 = ((base + P.first_off) >> 12) & 7;
-    B.span = P.dense_ok ? B.lead0 + (P.last_end - P.first_off) / kBlk : 0;
+    B.lead0 = obj_lead(base, P.first_off);
+    B.span = P.dense_ok ? dense_span(B.lead0, P.first_off, P.last_end) : 0;
     // layout: forced (s3dg_set_batch_tile) or least cost
     uint32_t tshift = kTileShiftMax;
     if (K.tile_shift == 0 && K.force_dense && P.dense_ok) tshift = 0;
@@ -300,5 +375,30 @@ inline BatchPlan plan_sub_batch(const BatchScan &P, uintptr_t base, const BatchK
                                                          : kZcNone;
     return B;
 }
+
+// The staged descriptors H[0, n) in the plan's order: the empty objects
+// squeezed out (m remain), then for two classes a stable partition, the
+// objects below `split` blocks first.
+inline void order_staging(s3dg_obj_desc *H, uint64_t n, uint64_t m, const BatchPlan &B, uint64_t split) {
+    if (m != n) {   // squeeze out the empty objects
+        uint64_t j = 0;
+        for (uint64_t i = 0; i < n; ++i)
+            if (H[i].size) H[j++] = H[i];
+    }
+    if (B.nclass == 2) {   // stable partition: small objects first
+        std::vector<s3dg_obj_desc> big;
+        big.reserve(B.cls[1].count);
+        uint64_t j = 0;
+        for (uint64_t i = 0; i < m; ++i) {
+            if (split_small(obj_blocks(H[i].size), split)) H[j++] = H[i];
+            else big.push_back(H[i]);
+        }
+        std::copy(big.begin(), big.end(), H + j);
+    }
+}
+
+// A call's descriptors are cut into sub-batches: 16 Ki objects first, doubling
+// to 256 Ki, so the host's pass over one overlaps the fill of the one before.
+constexpr uint64_t kBatchSubFirst = 16384, kBatchSubMax = 262144;
 
 }  // namespace s3dg

@@ -15,7 +15,7 @@ using namespace s3dg;
 namespace {
 
 // Mixed-size batch ("Batches"): the descriptors are cut into
-// sub-batches (16 Ki objects first, doubling to 256 Ki) so the host's pass
+// sub-batches (kBatchSubFirst objects first, doubling to kBatchSubMax) so the host's pass
 // over sub-batch k+1 overlaps the GPU's fill of sub-batch k.  Per sub-batch
 // the host makes one pass on up to 8 threads: it validates, counts slots and
 // copies the 40-B descriptors into pinned staging (empty ones squeezed out
@@ -24,14 +24,14 @@ namespace {
 // offset and k_batch_map derives prefix parameters and tile records.
 // Record layout per sub-batch (plan_sub_batch, s3dg_batch_plan.h):
 //   * tiles of 2^tshift blocks (2..64) per object, the object's block 0 at
-//     slot `lead` = its 4 KiB granule (mod 8): XCD-aligned, dead slots at
-//     both ends of every object;
+//     slot `lead` = its 4 KiB granule (mod 8): dead slots at both ends of
+//     every object, and XCD-aligned (slot = granule mod 8) from 8-block
+//     tiles up; forced 2- and 4-block tiles align mod 2 and mod 4 only;
 //   * dense (tshift 0): objects 4 KiB-aligned, sorted and non-overlapping;
 //     one record per 4 KiB granule of the sub-batch's address range, so slot
 //     = granule and only gaps are dead.
 // Descriptors are checked per sub-batch: on an error the objects of earlier
 // sub-batches may already be enqueued.
-constexpr uint64_t kBatchSubFirst = 16384, kBatchSubMax = 262144;
 
 // A few persistent host threads for the batch passes: run(parts, fn) calls
 // fn(0..parts-1), part 0 in the caller.  One run at a time; a second caller
@@ -149,27 +149,6 @@ BatchScan scan_sub_batch(const s3dg_obj_desc *d, uint64_t k0, uint64_t k1, uintp
     return batch_scan_merge(part, parts);
 }
 
-// The staged descriptors H[0, n) in the plan's order: the empty objects
-// squeezed out (m remain), then for two classes a stable partition, the
-// objects below `split` blocks first.
-void order_staging(s3dg_obj_desc *H, uint64_t n, uint64_t m, const BatchPlan &B, uint64_t split) {
-    if (m != n) {   // squeeze out the empty objects
-        uint64_t j = 0;
-        for (uint64_t i = 0; i < n; ++i)
-            if (H[i].size) H[j++] = H[i];
-    }
-    if (B.nclass == 2) {   // stable partition: small objects first
-        std::vector<s3dg_obj_desc> big;
-        big.reserve(B.cls[1].count);
-        uint64_t j = 0;
-        for (uint64_t i = 0; i < m; ++i) {
-            if ((H[i].size + kBlk - 1) / kBlk < split) H[j++] = H[i];
-            else big.push_back(H[i]);
-        }
-        std::copy(big.begin(), big.end(), H + j);
-    }
-}
-
 }  // namespace
 
 extern "C" int s3dg_fill_controlled_batch(s3dg_ctx *c, void *dst_base, const s3dg_obj_desc *d, uint64_t n,
@@ -197,7 +176,7 @@ extern "C" int s3dg_fill_controlled_batch(s3dg_ctx *c, void *dst_base, const s3d
         if (m == 0) continue;
         const BatchPlan B = plan_sub_batch(P, base, K);
         if (B.uniform) {   // a stream: no records per tile or granule
-            const uint64_t nb = (P.ufirst.size + kBlk - 1) / kBlk;
+            const uint64_t nb = obj_blocks(P.ufirst.size);
             PrefixParams pp;
             if (int r = make_prefix(nb, P.ufirst.dedup, P.ufirst.f_num, P.ufirst.f_den, &pp)) return r;
             if (int r = fill_uniform(c, (uint8_t *)dst_base + P.ufirst.dst_off, P.ufirst.size, P.ustride, m, pp,

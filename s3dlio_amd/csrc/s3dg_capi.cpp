@@ -73,14 +73,7 @@ int make_prefix(uint64_t nblocks, uint64_t dedup, uint32_t f_num, uint32_t f_den
     if (f_den == 0) return fail(S3DG_EINVAL, "f_den must be >= 1");
     if (f_num >= f_den) return fail(S3DG_EINVAL, "f_num must be < f_den (zero ratio < 1)");
     if (nblocks > 0xFFFFFFFFull) return fail(S3DG_EINVAL, "object larger than 2^32 blocks");
-    const uint64_t tot = (uint64_t)f_num * kBlk;
-    const uint64_t U = s3dg_unique_blocks(nblocks, dedup);
-    pp->unique = U == nblocks ? 0xFFFFFFFFu : (uint32_t)U;
-    pp->floor_len = (uint32_t)(tot / f_den);
-    pp->rem = (uint32_t)(tot % f_den);
-    pp->f_den = f_den;
-    pp->m_unique = fastmod_magic(pp->unique == 0xFFFFFFFFu ? 1u : pp->unique);
-    pp->m_fden = fastmod_magic(f_den);
+    *pp = prefix_params(nblocks, dedup, f_num, f_den);   // s3dg_prefix.h: the device's function too
     return S3DG_OK;
 }
 
@@ -155,11 +148,7 @@ static const char kBuildDigestRecord[] __attribute__((used)) = "S3DG_BUILD_DIGES
 const char *s3dg_build_digest(void) { return kBuildDigestRecord + sizeof("S3DG_BUILD_DIGEST=") - 1; }
 
 uint64_t s3dg_unique_blocks(uint64_t nblocks, uint64_t dedup) {
-    const uint64_t d = dedup == 0 ? 1 : dedup;
-    if (d <= 1) return nblocks;
-    double r = std::round((double)nblocks / (double)d);   // f64::round, half away
-    if (r < 1.0) r = 1.0;
-    return (uint64_t)r;
+    return unique_blocks(nblocks, dedup);
 }
 
 int s3dg_zero_class(uint32_t f_num, uint32_t f_den) { return zero_class(f_num, f_den); }

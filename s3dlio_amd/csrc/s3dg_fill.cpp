@@ -36,15 +36,14 @@ static int tiles_reserve(StreamState *S, uint64_t tiles, hipStream_t s) {
 // held: the stream's state when the caller already holds it (batch sub-batches).
 int fill_uniform(s3dg_ctx *c, uint8_t *dst, uint64_t obj_size, uint64_t stride, uint64_t n_objs,
                  const PrefixParams &pp, uint64_t seed_base, uint64_t first_obj, hipStream_t s, StreamState *held) {
-    const uint64_t nb = (obj_size + kBlk - 1) / kBlk;
-    const uint32_t lead = (uint32_t)(((uintptr_t)dst >> 12) & 7);
+    const uint64_t nb = obj_blocks(obj_size);
+    const uint32_t lead = (uint32_t)obj_lead((uintptr_t)dst, 0);   // the batch's record rules (s3dg_batch_plan.h)
     if (c->stream_tiles && (n_objs == 1 || stride % (8 * kBlk) == 0) && n_objs * nb >= kStreamTilesMinBlocks &&
         nb + lead < (1ull << 31)) {
         uint64_t ntiles[kTileShiftMax + 1] = {};
-        for (uint32_t sh = kTileShiftMin; sh <= kTileShiftMax; ++sh)
-            ntiles[sh] = n_objs * ((nb + lead + (1ull << sh) - 1) >> sh);
+        for (uint32_t sh = kTileShiftMin; sh <= kTileShiftMax; ++sh) ntiles[sh] = n_objs * obj_tiles(nb, lead, sh);
         const uint32_t tshift = c->tile_shift ? c->tile_shift : pick_tile_shift(ntiles);
-        const uint64_t tpo = (nb + lead + (1ull << tshift) - 1) >> tshift;
+        const uint64_t tpo = obj_tiles(nb, lead, tshift);
         std::unique_ptr<StreamLock> SL;
         if (!held) SL.reset(new StreamLock(c, s));
         StreamState *S = held ? held : SL->get();

@@ -12,6 +12,7 @@
 #include "s3dg_dgen_batch_plan.h"   // DgenChunkRec, the batch's lane limits
 #include "s3dg_ks_plan.h"           // the uniform keystream launches' plan, fastmod
 #include "s3dg_crc_batch_plan.h"    // CrcBatchCounts, the batch CRC's table
+#include "s3dg_prefix.h"            // PrefixParams and the one function that makes them
 
 // Sets the calling thread's error text (s3dg_last_error) and returns code.
 extern "C" int s3dg_internal_fail(int code, const char *msg);
@@ -24,17 +25,7 @@ constexpr uint32_t kMod = 32;     // MOD_SIZE   src/constants.rs:352
 constexpr uint64_t kDgenBlock = 1ull << 20;   // DGEN_BLOCK_SIZE src/constants.rs:348
 constexpr int kWavesPerWG = 4;
 
-// Zero-prefix parameters of one object: const_len(u) =
-//   floor_len + ((u+1)*rem)/f_den - (u*rem)/f_den   (closed form of the
-// accumulator at src/data_gen.rs:174-190; rem < f_den).
-struct PrefixParams {
-    uint32_t unique;     // U, src/data_gen.rs:162-167 (0xFFFFFFFF: U == nblocks, u = i)
-    uint32_t floor_len;
-    uint32_t rem;
-    uint32_t f_den;      // 0: generate_random_data block layout (src/data_gen.rs:102-132)
-    uint64_t m_unique;   // Lemire fastmod constants: floor(2^64 / d) + 1
-    uint64_t m_fden;
-};
+// PrefixParams, the zero-prefix parameters of one object: s3dg_prefix.h
 
 // Batch sub-batches reach the device as the caller's 40-B descriptors
 // (empty objects dropped); the record ranges are derived there:

@@ -473,11 +473,16 @@ __global__ __launch_bounds__(64 * NW) void k_verify_stream(const uint8_t *src, c
 
 // Batch: workgroup g -> tile record g >> tshift (one scalar load), block
 // first + (g mod 2^tshift) - lead of that object; slots before the object's
-// start (lead) or past its end exit.  lead makes g = 4 KiB-granule address
-// (mod 8), as in the stream kernel: workgroups are dealt round-robin to the
-// 8 XCDs, so XCD x writes only granules = x (mod 8).
-// Tiles are 2^tshift blocks (2..64, chosen per launch by the host so the
-// dead workgroups of ragged object tails stay few).
+// start (lead) or past its end exit (slot_block, s3dg_batch_plan.h, restates
+// the expression).  lead makes g = 4 KiB-granule address (mod 8) for the dense
+// layout and tiles of 8 blocks and more, as in the stream kernel: workgroups
+// are dealt round-robin to the 8 XCDs, so XCD x writes only granules = x
+// (mod 8).  With forced 2- and 4-block tiles an object's first
+// slot is a multiple of the tile only, so g = granule holds mod 2 and mod 4
+// (tests/capi/batch_records_sweep.cpp asserts both).
+// Tiles are 2^tshift blocks (8..64 chosen per launch by the host so the
+// dead workgroups of ragged object tails stay few, 2 and 4 forced only;
+// DESIGN.md §5.1).
 // pf > 0: the first 8 workgroups of every 256 blocks (one per XCD: workgroups
 // are dealt round-robin to the XCDs) touch the records of the 256 blocks
 // 64*pf blocks ahead (one lane per 128-byte line of records) after their
@@ -659,38 +664,20 @@ __global__ __launch_bounds__(64 * NW) void k_verify_batch(const uint8_t *src_bas
     }
 }
 
-// Prefix parameters of one object on the device, as the host's make_prefix
-// (src/data_gen.rs:162-175; s3dg_unique_blocks' f64 round half away from zero).
-__device__ PrefixParams dev_make_prefix(uint64_t nb, uint64_t dedup, uint32_t f_num, uint32_t f_den) {
-    const uint64_t d = dedup == 0 ? 1 : dedup;
-    uint64_t U = nb;
-    if (d > 1) {
-        double r = round((double)nb / (double)d);
-        if (r < 1.0) r = 1.0;
-        U = (uint64_t)r;
-    }
-    PrefixParams pp;
-    const uint64_t tot = (uint64_t)f_num * kBlk;
-    pp.unique = U == nb ? 0xFFFFFFFFu : (uint32_t)U;
-    pp.floor_len = (uint32_t)(tot / f_den);
-    pp.rem = (uint32_t)(tot % f_den);
-    pp.f_den = f_den;
-    pp.m_unique = ~0ull / (pp.unique == 0xFFFFFFFFu ? 1u : pp.unique) + 1;
-    pp.m_fden = ~0ull / f_den + 1;
-    return pp;
-}
+// Prefix parameters of one object on the device: prefix_params (s3dg_prefix.h),
+// the host's make_prefix.
 
 // Records of a batch sub-batch from its uploaded descriptors, one thread per
 // object: record q in [rec_lo, rec_hi) maps slot (q << tshift) + k to block
-// (q - rec_lo) << tshift + k - lead.  Tile layouts: rec_lo from the scan, lead
-// = the object's granule mod 8 (XCD alignment).  Dense: rec_lo = the object's
-// granule slot (0 for the first object, whose lead is lead0), rec_hi = the
-// next object's, so the gap records before it are its dead slots.
-// An object with few records writes them itself; the records of objects with
-// more (a multi-GiB object, a dense layout with large gaps) are written by the
-// whole wave, 64 per pass, so no lane loops over tens of thousands of them
-// while the fill waits.
-constexpr uint64_t kMapOwnRecords = 16;
+// (q - rec_lo) << tshift + k - lead.  The ranges are the record rules of
+// s3dg_batch_plan.h (tiled_records, dense_records).  Tile layouts: rec_lo from
+// the scan, lead = the object's granule mod 8 (XCD alignment).  Dense: rec_lo =
+// the object's granule slot (0 for the first object, whose lead is lead0),
+// rec_hi = the next object's, so the gap records before it are its dead slots.
+// An object with few records (map_own_records) writes them itself; the records
+// of objects with more (a multi-GiB object, a dense layout with large gaps) are
+// written by the whole wave, 64 per pass, so no lane loops over tens of
+// thousands of them while the fill waits.
 __global__ __launch_bounds__(256) void k_batch_map(const s3dg_obj_desc *d, uint64_t n, const uint64_t *scan,
                                                    TileRec *tiles, uint32_t tshift, uint64_t base, uint64_t lead0,
                                                    uint64_t first_off) {
@@ -700,25 +687,19 @@ __global__ __launch_bounds__(256) void k_batch_map(const s3dg_obj_desc *d, uint6
     uint64_t rec_lo = 0, rec_hi = 0;
     if (k < n) {
         const s3dg_obj_desc o = d[k];
-        const uint64_t nb = (o.size + kBlk - 1) / kBlk;
-        uint64_t lead;
-        if (tshift == 0) {
-            const uint64_t g0 = lead0 + (o.dst_off - first_off) / kBlk;
-            rec_lo = k == 0 ? 0 : g0;
-            rec_hi = k + 1 < n ? lead0 + (d[k + 1].dst_off - first_off) / kBlk : g0 + nb;
-            lead = g0 - rec_lo;
-        } else {
-            lead = ((base + o.dst_off) >> 12) & 7;
-            rec_lo = scan[k];
-            rec_hi = rec_lo + ((nb + lead + (1ull << tshift) - 1) >> tshift);
-        }
+        const uint64_t nb = obj_blocks(o.size);
+        const RecRange R = tshift == 0 ? dense_records(k == 0, lead0, first_off, o.dst_off, nb, k + 1 < n,
+                                                       k + 1 < n ? d[k + 1].dst_off : 0)
+                                       : tiled_records(scan[k], nb, base, o.dst_off, tshift);
+        rec_lo = R.lo;
+        rec_hi = R.hi;
         r.dst_off = o.dst_off;
         r.size = o.size;
         r.entropy = o.entropy;
-        r.lead = (uint32_t)lead;
-        r.pp = dev_make_prefix(nb, o.dedup, o.f_num, o.f_den);
+        r.lead = (uint32_t)R.lead;
+        r.pp = prefix_params(nb, o.dedup, o.f_num, o.f_den);
     }
-    const bool own = rec_hi - rec_lo <= kMapOwnRecords;
+    const bool own = map_own_records(rec_hi - rec_lo);
     if (own)
         for (uint64_t q = rec_lo; q < rec_hi; ++q) {
             r.first = (uint32_t)((q - rec_lo) << tshift);
@@ -762,10 +743,10 @@ __global__ __launch_bounds__(256) void k_verify_batch_map(const s3dg_obj_desc *d
             r.size = o.size;
             r.entropy = o.entropy;
             r.obj = (uint32_t)k;
-            r.pp = dev_make_prefix((o.size + kBlk - 1) / kBlk, o.dedup, o.f_num, o.f_den);
+            r.pp = prefix_params(obj_blocks(o.size), o.dedup, o.f_num, o.f_den);
         }
     }
-    const bool own = rec_hi - rec_lo <= kMapOwnRecords;
+    const bool own = map_own_records(rec_hi - rec_lo);
     if (own)
         for (uint64_t q = rec_lo; q < rec_hi; ++q) {
             r.first = (uint32_t)((q - rec_lo) << tshift);

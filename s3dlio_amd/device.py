@@ -357,8 +357,11 @@ class Context:
         call("s3dg_set_stream_tiles", self._h, int(on))
 
     def set_batch_tile(self, blocks: int = 0) -> None:
-        """Blocks per batch tile record: 8, 16, 32, 64, or 0 = chosen per launch;
-        results are identical."""
+        """Blocks per batch tile record: 2, 4, 8, 16, 32 or 64 forced, 1 = the dense
+        layout (one record per 4 KiB granule) where the objects allow it, or 0 =
+        chosen per launch (8..64 or dense).  2- and 4-block tiles keep a slot
+        equal to its granule modulo 2 and 4 only, not modulo 8.  Results are
+        identical."""
         call("s3dg_set_batch_tile", self._h, int(blocks))
 
     def set_batch_split(self, blocks: int = -1) -> None:
