@@ -18,7 +18,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libs3dlio_amd.so")
-SOURCES = [os.path.join(CSRC, "s3dg_kernels.hip"), os.path.join(CSRC, "s3dg_capi.cpp"),
+SOURCES = [os.path.join(CSRC, "s3dg_ks_kernels.hip"), os.path.join(CSRC, "s3dg_block.hip"),
+           os.path.join(CSRC, "s3dg_capi.cpp"),
            os.path.join(CSRC, "s3dg_tune.cpp"), os.path.join(CSRC, "s3dg_fill.cpp"),
            os.path.join(CSRC, "s3dg_batchfill.cpp"), os.path.join(CSRC, "s3dg_keystream.cpp"),
            os.path.join(CSRC, "s3dg_jump.cpp"), os.path.join(CSRC, "s3dg_generator.cpp"),
@@ -30,7 +31,8 @@ SOURCES = [os.path.join(CSRC, "s3dg_kernels.hip"), os.path.join(CSRC, "s3dg_capi
            os.path.join(CSRC, "s3dg_chunks.cpp"), os.path.join(CSRC, "s3dg_lz.hip"),
            os.path.join(CSRC, "s3dg_lz.cpp"), os.path.join(CSRC, "s3dg_verify_batch.cpp"),
            os.path.join(CSRC, "s3dg_dgen_batch.cpp"), os.path.join(CSRC, "s3dg_crc_batch.cpp")]
-HEADERS = [os.path.join(CSRC, "s3dg_internal.h"), os.path.join(CSRC, "s3dg_ctx.h"),
+HEADERS = [os.path.join(CSRC, "s3dg_internal.h"), os.path.join(CSRC, "s3dg_dev.h"),
+           os.path.join(CSRC, "s3dg_ctx.h"),
            os.path.join(CSRC, "s3dg_batch_plan.h"), os.path.join(CSRC, "s3dg_ks_verify_plan.h"),
            os.path.join(CSRC, "s3dg_jump.h"), os.path.join(CSRC, "s3dg_measure_plan.h"),
            os.path.join(CSRC, "s3dg_measure.h"), os.path.join(CSRC, "s3dg_fp.h"),
@@ -124,18 +126,24 @@ def build_native_loop(force: bool = False, verbose: bool = False) -> str:
     return NL_LIB
 
 
+def compile_flags(root: str = ROOT) -> list[str]:
+    """hipcc flags of every translation unit of the tree at `root` (this one,
+    or another checkout whose kernels tools/kernel_streams.py compares)."""
+    return [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
+            "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
+            # kernel arguments preloaded into SGPRs (gfx950): the first scalar
+            # load of every 4 KiB-block workgroup disappears from its critical path
+            "-mllvm", "-amdgpu-kernarg-preload-count=16",
+            "-I", os.path.join(root, "include"), "-I", os.path.join(root, "s3dlio_amd", "csrc"),
+            "-DS3DG_BUILD"]
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     build_bytesview(force, verbose)
     build_native_loop(force, verbose)
     if not force and not _stale():
         return LIB
-    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
-             "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
-             # kernel arguments preloaded into SGPRs (gfx950): the first scalar
-             # load of every 4 KiB-block workgroup disappears from its critical path
-             "-mllvm", "-amdgpu-kernarg-preload-count=16",
-             "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-             "-DS3DG_BUILD", f"-DS3DG_BUILD_DIGEST=\"{source_digest()}\""]
+    flags = compile_flags() + [f"-DS3DG_BUILD_DIGEST=\"{source_digest()}\""]
     # one translation unit per process (no device code crosses units), then link
     import concurrent.futures as cf
     import tempfile

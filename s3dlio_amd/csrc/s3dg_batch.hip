@@ -1,7 +1,7 @@
 // s3dg_batch.hip — device side of the batch record layout:
 // the exclusive scan that turns a sub-batch's descriptors into record offsets
-// (hipCUB device scan over a transform of the 40-B descriptors).  Split from
-// s3dg_kernels.hip so the library templates compile once.
+// (hipCUB device scan over a transform of the 40-B descriptors).  A unit apart
+// from s3dg_block.hip so the library templates compile once.
 #include <hipcub/hipcub.hpp>
 
 #include "s3dg_internal.h"

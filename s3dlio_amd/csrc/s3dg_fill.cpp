@@ -314,8 +314,8 @@ int s3dg_write_ceiling_fill(s3dg_ctx *c, void *dst, uint64_t len, uint32_t pace,
     if (int r = tiles_reserve(S, n_objs * tpo, s)) return r;
     LaunchCfg lc = cfg_for(c, true);
     lc.pace = pace;
-    HIP_TRY(launch_fill_uniform_tiles_ablated(lc, (uint8_t *)dst, obj, kObj, n_objs, (uint32_t)tpo,
-                                              tshift, lead, pp, S->tiles, c->base_dev, s),
+    HIP_TRY(launch_fill_uniform_tiles(lc, (uint8_t *)dst, obj, kObj, n_objs, (uint32_t)tpo, tshift, lead, 0, pp,
+                                      S->tiles, c->base_dev, s, true),
             "launch k_fill_batch(ablated)");
     return S3DG_OK;
 }

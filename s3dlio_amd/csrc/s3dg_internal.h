@@ -129,16 +129,12 @@ hipError_t launch_batch_tiles(const LaunchCfg &lc, uint8_t *dst_base, uint64_t t
                               TileRec *tiles, const void *base_dev, hipStream_t s);
 
 // A uniform stream through the batch kernel: records built on the device
-// (k_tile_map_uniform), then k_fill_batch.
+// (k_tile_map_uniform), then k_fill_batch.  ablated: the
+// store-only reference of the same launch (s3dg_write_ceiling_fill, ent0 = 0).
 hipError_t launch_fill_uniform_tiles(const LaunchCfg &lc, uint8_t *dst, uint64_t obj_size, uint64_t stride,
                                      uint64_t n_objs, uint32_t tiles_per_obj, uint32_t tshift, uint32_t lead,
                                      uint64_t ent0, PrefixParams pp, TileRec *tiles, const void *base_dev,
-                                     hipStream_t s);
-
-// The store-only reference of the same launch (s3dg_write_ceiling_fill).
-hipError_t launch_fill_uniform_tiles_ablated(const LaunchCfg &lc, uint8_t *dst, uint64_t obj_size, uint64_t stride,
-                                             uint64_t n_objs, uint32_t tiles_per_obj, uint32_t tshift, uint32_t lead,
-                                             PrefixParams pp, TileRec *tiles, const void *base_dev, hipStream_t s);
+                                     hipStream_t s, bool ablated = false);
 
 // K2 keystream launch: chunks [chunk0, chunk0 + nchunks) of an obj_len-byte
 // object, chunk k at dst + (k - chunk0) * chunk_bytes.

@@ -37,7 +37,7 @@ constexpr uint64_t kKsMinSpan = 256;          // fewest draws per lane for small
 constexpr uint64_t kDgenPrefixMinDraws = 512;
 constexpr uint32_t kKsMaxLpc = 1024;          // lanes per chunk at most: 16 waves
 // Launches of at least this many rounds of resident 1-wave workgroups run a
-// persistent grid by default (the measurements are in s3dg_kernels.hip).
+// persistent grid by default (the measurements are in s3dg_ks_kernels.hip).
 #ifndef S3DG_KS_PERSIST_ROUNDS
 #define S3DG_KS_PERSIST_ROUNDS 6
 #endif

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Diagnostic: build the product kernels with parts compiled out
-(-DS3DG_ABLATE=k, see s3dg_kernels.hip) and time cfg2-shaped fills of each
+(-DS3DG_ABLATE=k, see s3dg_dev.h) and time cfg2-shaped fills of each
 variant interleaved in one process.  Tooling only; outputs are wrong by design."""
 import ctypes, json, os, statistics, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "tools", "_build")
-VARIANTS = os.environ.get("ABLATE_VARIANTS", "0,1,2,3").split(",")   # S3DG_ABLATE bits (s3dg_kernels.hip)
+VARIANTS = os.environ.get("ABLATE_VARIANTS", "0,1,2,3").split(",")   # S3DG_ABLATE bits (s3dg_dev.h; bits 0-4: s3dg_block.hip)
 
 
 def build():

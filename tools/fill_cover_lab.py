@@ -39,13 +39,13 @@ def build():
         shutil.rmtree(SRC)
     shutil.copytree(CSRC, os.path.join(SRC, "csrc"))
     shutil.copytree(os.path.join(ROOT, "include"), os.path.join(SRC, "include"))
-    k = os.path.join(SRC, "csrc", "s3dg_kernels.hip")
+    k = os.path.join(SRC, "csrc", "s3dg_block.hip")
     s = open(k).read()
     decl = ("__device__ unsigned int *g_cov;\n__device__ unsigned long long g_cov_n;\n"
             "__device__ unsigned long long *g_cov_exit;   // [0] count, [1] max slot, then NLOG x 18 words\n")
-    anchor0 = "namespace s3dg {\n#if S3DG_KS_TRACE"
+    anchor0 = "namespace s3dg {\nnamespace {\n"
     assert s.count(anchor0) == 1
-    s = s.replace(anchor0, "namespace s3dg {\n" + decl + "#if S3DG_KS_TRACE", 1)
+    s = s.replace(anchor0, "namespace s3dg {\n" + decl + "namespace {\n", 1)
     ex = "    if (ib < 0 || (uint64_t)ib * kBlk >= e.size) return;   // uniform for the whole workgroup\n"
     assert s.count(ex) == 1, "early exit not found"
     s = s.replace(ex, (
@@ -61,7 +61,7 @@ def build():
         "        }\n"
         "        return;\n"
         "    }\n") % NLOG, 1)
-    anchor = "\n}\n\n// Prefix parameters of one object on the device"
+    anchor = "\n}\n\n// Batch verify, the read-side twin of k_fill_batch"
     assert s.count(anchor) == 1, "k_fill_batch end not found"
     s = s.replace(anchor, "\n    if (!ABL && t == 0 && g_cov) {\n"
                   "        const uint64_t gi = ((uint64_t)(bdst - dst_base) >> 12);\n"

@@ -39,10 +39,10 @@ def build():
     shutil.copytree(os.path.join(ROOT, "include"), os.path.join(SRC, "include"))
     c = os.path.join(SRC, "csrc")
     patch(os.path.join(c, "s3dg_internal.h"), "    uint32_t par;\n", "    uint32_t par;\n    uint32_t xres;          // lab: lanes on their XCD's granules\n")
-    patch(os.path.join(c, "s3dg_kernels.hip"), "    const uint64_t gl = (bid * W + w) * 64 + l;",
+    patch(os.path.join(c, "s3dg_ks_kernels.hip"), "    const uint64_t gl = (bid * W + w) * 64 + l;",
           "    const uint64_t wi_ = bid * W + w;\n"
           "    const uint64_t gl = A.xres ? (((wi_ >> 3) << lsh) + (wi_ & 7) + 8 * (uint64_t)l) : wi_ * 64 + l;")
-    patch(os.path.join(c, "s3dg_kernels.hip"), "        X.xg = xg;", "        X.xg = X.xres ? 1 : xg;")
+    patch(os.path.join(c, "s3dg_ks_kernels.hip"), "        X.xg = xg;", "        X.xg = X.xres ? 1 : xg;")
     patch(os.path.join(c, "s3dg_keystream.cpp"), "    A.lpc = lpc;\n    A.span = (uint32_t)span;\n    A.z0 = z0;",
           "    A.lpc = lpc;\n    A.span = (uint32_t)span;\n    A.z0 = z0;\n"
           "    A.xres = getenv(\"S3DG_KS_XRES\") && mode == 0 && lpc == 512 && z0 == 0 ? 1u : 0u;")

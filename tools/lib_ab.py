@@ -36,9 +36,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "tools", "_build")
 DEFAULT = "r02=aa93058;r03=dedd5d0;head=."
-SRC_NAMES = ["s3dg_kernels.hip", "s3dg_capi.cpp", "s3dg_tune.cpp", "s3dg_fill.cpp", "s3dg_batchfill.cpp",
-             "s3dg_keystream.cpp", "s3dg_jump.cpp", "s3dg_generator.cpp", "s3dg_crc.hip",
-             "s3dg_npz.cpp", "s3dg_object.cpp", "s3dg_put.cpp", "s3dg_numa.cpp", "s3dg_host.cpp", "s3dg_batch.hip"]
 
 
 def variants():
@@ -66,6 +63,15 @@ def sources(ref):
     return os.path.join(dst, "include"), os.path.join(dst, "s3dlio_amd", "csrc")
 
 
+def units(ref, csrc):
+    """The library's translation units: this tree's build.SOURCES, or, for
+    another commit (whose unit list may differ), every .hip / .cpp of its csrc."""
+    if ref == ".":
+        from s3dlio_amd.build import SOURCES
+        return list(SOURCES)
+    return sorted(os.path.join(csrc, s) for s in os.listdir(csrc) if s.endswith((".hip", ".cpp")))
+
+
 def build():
     os.makedirs(OUT, exist_ok=True)
     procs = []
@@ -73,8 +79,7 @@ def build():
         inc, csrc = sources(ref)
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-fvisibility=hidden", "-Wno-unused-function", "-mllvm", "-amdgpu-kernarg-preload-count=16",
-               "-I", inc, "-I", csrc, "-DS3DG_BUILD", *flags, "-o", so(name)] + [
-                   os.path.join(csrc, s) for s in SRC_NAMES if os.path.exists(os.path.join(csrc, s))]
+               "-I", inc, "-I", csrc, "-DS3DG_BUILD", *flags, "-o", so(name)] + units(ref, csrc)
         procs.append(subprocess.Popen(cmd))
         if len(procs) >= 3:
             assert procs.pop(0).wait() == 0
