@@ -763,6 +763,66 @@ int s3dg_crc32_batch(s3dg_ctx *ctx, const void *src_base, const s3dg_span *spans
                      uint32_t *crcs);
 int s3dg_crc32_batch_async(s3dg_ctx *ctx, const void *src_base, const s3dg_span *spans, uint64_t n, void *stream,
                            uint32_t *crcs_dev);
+/* ---- TFRecord shards framed and checked on the device ----
+ * Shard k is `records` records of `record_size` payload bytes.  Its framed
+ * stream is byte-identical to build_tfrecord_with_index(records, record_size,
+ * payload) (src/data_formats/tfrecord.rs:10-75): record i is
+ *   u64 len | masked_crc(len) | data | masked_crc(data)
+ * at i * (16 + record_size), and its index entry is <u64 i * (16 + record_size),
+ * u64 16 + record_size>.  record_size == 0 is a valid 16-byte record.  One
+ * kernel hashes and, in the frame form, copies every record; a record of more
+ * than one region (32 KiB or more) is finished by a second, small launch.
+ * The whole-file checksum of a shard is s3dg_crc32_batch over its dst span. */
+typedef struct {
+    uint64_t src_off;      /* payload: records * record_size bytes at src_base + src_off */
+    uint64_t dst_off;      /* framed stream: records * (16 + record_size) bytes at dst_base + dst_off */
+    uint64_t idx_off;      /* index: 16 * records bytes at idx_base + idx_off (unused when idx_base is NULL) */
+    uint64_t records;
+    uint64_t record_size;
+} s3dg_tfrecord_shard;
+typedef struct {
+    uint64_t records;          /* records looked at */
+    uint64_t bad_records;      /* records with at least one of the three below */
+    uint64_t bad_length;       /* length field differs from record_size */
+    uint64_t bad_length_crc;   /* length CRC differs from masked_crc of record_size's 8 bytes */
+    uint64_t bad_data_crc;     /* footer differs from masked_crc of the record's data */
+    uint64_t first_shard;      /* caller's index of the first shard with a bad record; UINT64_MAX when clean */
+    uint64_t first_record;     /* the lowest bad record of that shard; UINT64_MAX when clean */
+} s3dg_tfrecord_result;
+/* records * (16 + record_size); S3DG_EINVAL when that overflows or out is null. */
+int s3dg_tfrecord_size(uint64_t records, uint64_t record_size, uint64_t *out);
+/* Frames every shard of the list in one call.  Ordered on `stream`, returns
+ * without a wait; `shards` is consumed before it returns.  Shards may come in
+ * any order and may be empty (records == 0: nothing is looked at or written);
+ * two shards may share a source.  src_base, dst_base and idx_base (nullable:
+ * no index) are 16-byte aligned device pointers; src_off, dst_off and idx_off
+ * are multiples of 16.
+ * Writes exactly the bytes of each stream and each index: no byte before
+ * dst_off, none at or past the stream's ragged end (a neighbour may start 16
+ * bytes later), and every byte once.  Reads no source byte outside
+ * [src_off, src_off + records * record_size).  Destination streams must not
+ * overlap each other or any source span (the caller's contract); overlap of a
+ * shard's own source and stream is refused.
+ * Refusals (S3DG_EINVAL, each with a message; every descriptor is checked
+ * before anything is reserved or enqueued, so a refused call has read and
+ * written nothing): "null context", a null or misaligned base, "null shard
+ * array", and per shard ("shard k: ...") an offset that is no multiple of 16,
+ * record_size above 2^31 x 4096, records * (16 + record_size) or an end
+ * address overflowing, more than 2^46 framed bytes in one call.  n == 0
+ * succeeds whatever the other pointers. */
+int s3dg_tfrecord_frame_batch(s3dg_ctx *ctx, const void *src_base, void *dst_base, void *idx_base,
+                              const s3dg_tfrecord_shard *shards, uint64_t n, void *stream);
+/* The read-side twin over the same descriptors: dst_off, records and
+ * record_size are used, the stream is at base + dst_off.  Synchronous on
+ * `stream`; writes nothing to the streams, and a clean stream costs no store
+ * and no atomic.  Per record: the length field against record_size, the
+ * length CRC against record_size's, the data's CRC against the footer; a
+ * descriptor whose record_size is not the stream's shows as bad_length.
+ * total (required) sums the shards, with the first bad shard by the caller's
+ * index; per_shard (host array of n, or NULL) gets every shard's own result,
+ * first_shard being k or UINT64_MAX.  Refusals as above, and "null output". */
+int s3dg_tfrecord_check_batch(s3dg_ctx *ctx, const void *base, const s3dg_tfrecord_shard *shards, uint64_t n,
+                              void *stream, s3dg_tfrecord_result *total, s3dg_tfrecord_result *per_shard);
 /* zlib crc32_combine: CRC of A||B from crc(A), crc(B), |B| (host). */
 uint32_t s3dg_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2);
 /* Host CRC-32 update (crc32fast::Hasher semantics: start from 0). */

@@ -58,6 +58,18 @@ class Span(ctypes.Structure):
     _fields_ = [("off", c_u64), ("size", c_u64)]
 
 
+class TfrShard(ctypes.Structure):
+    """s3dg_tfrecord_shard"""
+    _fields_ = [("src_off", c_u64), ("dst_off", c_u64), ("idx_off", c_u64), ("records", c_u64),
+                ("record_size", c_u64)]
+
+
+class TfrRec(ctypes.Structure):
+    """s3dg_tfrecord_result"""
+    _fields_ = [("records", c_u64), ("bad_records", c_u64), ("bad_length", c_u64), ("bad_length_crc", c_u64),
+                ("bad_data_crc", c_u64), ("first_shard", c_u64), ("first_record", c_u64)]
+
+
 class MeasureRec(ctypes.Structure):
     """s3dg_measure_result"""
     _fields_ = [("bytes", c_u64), ("zero_bytes", c_u64), ("blocks", c_u64), ("unique_blocks", c_u64),
@@ -188,6 +200,10 @@ SIGNATURES = {
     "s3dg_crc32": (c_int, [c_vp, c_vp, c_u64, c_vp, ctypes.POINTER(c_u32)]),
     "s3dg_crc32_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(Span), c_u64, c_vp, ctypes.POINTER(c_u32)]),
     "s3dg_crc32_batch_async": (c_int, [c_vp, c_vp, ctypes.POINTER(Span), c_u64, c_vp, c_vp]),
+    "s3dg_tfrecord_size": (c_int, [c_u64, c_u64, ctypes.POINTER(c_u64)]),
+    "s3dg_tfrecord_frame_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(TfrShard), c_u64, c_vp]),
+    "s3dg_tfrecord_check_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(TfrShard), c_u64, c_vp,
+                                          ctypes.POINTER(TfrRec), ctypes.POINTER(TfrRec)]),
     "s3dg_crc32_combine": (c_u32, [c_u32, c_u32, c_u64]),
     "s3dg_crc32_host": (c_u32, [c_u32, c_vp, c_u64]),
     "s3dg_npz_size": (c_int, [ctypes.POINTER(c_u64), c_int, ctypes.c_char_p, c_u64,

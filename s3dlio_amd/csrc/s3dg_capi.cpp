@@ -122,6 +122,12 @@ void stream_state_free(StreamState *S) {
         if (T.uploaded) (void)hipEventDestroy(T.uploaded);
     }
     if (S->crc_out) (void)hipFree(S->crc_out);
+    for (auto &T : S->ttab) {
+        if (T.host) (void)hipHostFree(T.host);
+        if (T.dev) (void)hipFree(T.dev);
+        if (T.uploaded) (void)hipEventDestroy(T.uploaded);
+    }
+    if (S->tfr_out) (void)hipFree(S->tfr_out);
     delete S;
 }
 

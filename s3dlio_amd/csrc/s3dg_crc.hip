@@ -397,6 +397,9 @@ uint32_t x8n(uint64_t n) {
 }
 
 constexpr size_t kByteShiftOff = sizeof(CrcTables) + 64 * 4 + sizeof(CrcTablesCF);
+static_assert(kCrcTabLaneShiftOff == sizeof(CrcTables) && kCrcTabCfOff == sizeof(CrcTables) + 64 * 4 &&
+                  kCrcTabByteShiftOff == kByteShiftOff,
+              "the table offsets other units use (s3dg_internal.h)");
 
 uint32_t crc_tables[8][256];
 bool tables_ready = false;

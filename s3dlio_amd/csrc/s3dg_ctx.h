@@ -2,7 +2,7 @@
 // state and the measured defaults.  Private to the units that implement
 // include/s3dlio_gpu.h over the context (s3dg_capi.cpp, s3dg_tune.cpp,
 // s3dg_fill.cpp, s3dg_batchfill.cpp, s3dg_verify_batch.cpp, s3dg_keystream.cpp,
-// s3dg_dgen_batch.cpp, s3dg_crc_batch.cpp,
+// s3dg_dgen_batch.cpp, s3dg_crc_batch.cpp, s3dg_tfrecord.cpp,
 // and, through s3dg_accum.h, s3dg_measure.cpp, s3dg_chunks.cpp and
 // s3dg_lz.cpp); everything else
 // reaches a context through the functions of s3dg_internal.h.
@@ -200,6 +200,13 @@ struct StreamState {
     int cnext = 0;
     uint32_t *crc_out = nullptr;
     uint64_t crc_out_cap = 0;
+    // tables of TFRecord frame and check calls (s3dg_tfrecord.cpp), kept the
+    // same way ([shard entries | raw CRCs of long records]); and the per-shard
+    // records of the check form, which drains the stream
+    CrcTable ttab[2];
+    int tnext = 0;
+    TfrDevRes *tfr_out = nullptr;
+    uint64_t tfr_out_cap = 0;
     // lifetime (under the context's mu): users holding the state, and whether
     // s3dg_stream_release has taken it out of the context's map; the last
     // holder of a released state drains the stream and frees it

@@ -12,6 +12,7 @@
 #include "s3dg_dgen_batch_plan.h"   // DgenChunkRec, the batch's lane limits
 #include "s3dg_ks_plan.h"           // the uniform keystream launches' plan, fastmod
 #include "s3dg_crc_batch_plan.h"    // CrcBatchCounts, the batch CRC's table
+#include "s3dg_tfrecord_plan.h"     // TfrCounts, the TFRecord calls' table
 #include "s3dg_prefix.h"            // PrefixParams and the one function that makes them
 
 // Sets the calling thread's error text (s3dg_last_error) and returns code.
@@ -370,6 +371,23 @@ void crc_seg_fold(const CrcSegPlan &P, const uint32_t *regions, const uint8_t *c
 // crcs_dev[its k] (device or pinned host memory).  Nothing for C.live == 0.
 hipError_t crc_batch_launch(const uint8_t *src_base, const uint8_t *table_dev, const CrcBatchCounts &C, void *tab_dev,
                             int cus, uint32_t *crcs_dev, hipStream_t s);
+// The device tables of crc_tables_device, in bytes from their start:
+// [byte and row tables, 20 KiB][lane shifts, 256 B][single-bank tables, 64 KiB][byte shifts, 64 B].
+constexpr size_t kCrcTabLaneShiftOff = 20 * 256 * 4, kCrcTabCfOff = kCrcTabLaneShiftOff + 64 * 4,
+                 kCrcTabByteShiftOff = kCrcTabCfOff + 2 * 256 * 32 * 4;
+
+// ---- TFRecord shards (s3dg_tfrecord.hip; s3dg_tfrecord_plan.h) -----------------
+// One bad record's worth of a shard's check result, at the caller's index;
+// reset to zeros: first_inv is ~(lowest bad record), kept by atomicMax.
+struct TfrDevRes {
+    unsigned long long bad_records, bad_length, bad_length_crc, bad_data_crc, first_inv;
+};
+// table_dev is the uploaded shard entries with room for the long records' raw
+// CRCs behind it (tfr_device_bytes).  frame: src -> dst (+ idx, nullable);
+// check (dst == nullptr): reads src, adds to res[entry's k].  One launch over
+// the regions and, when the call has long records, one thread per such record.
+hipError_t tfrecord_launch(bool frame, const uint8_t *src, uint8_t *dst, uint8_t *idx, const uint8_t *table_dev,
+                           const TfrCounts &C, void *tab_dev, int cus, TfrDevRes *res, hipStream_t s);
 
 // ---- NUMA placement of host buffers (s3dg_numa.cpp) -------------------------
 bool device_local_cpus(int device, cpu_set_t *out);

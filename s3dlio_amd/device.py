@@ -201,6 +201,63 @@ class LzResult:
 
 
 CHUNK_DEFAULTS = (2048, 8192, 65536)   # min_bytes, avg_bytes, max_bytes
+@dataclass(frozen=True)
+class TfRecordResult:
+    """What Context.tfrecord_check_batch found (s3dg_tfrecord_result): the
+    totals over the list and, unless it was called with per_shard=False, every
+    shard that is not clean."""
+    records: int = 0
+    bad_records: int = 0          # records bad in at least one of the three classes below
+    bad_length: int = 0           # length field differs from record_size
+    bad_length_crc: int = 0       # length CRC differs from record_size's
+    bad_data_crc: int = 0         # footer differs from the data's masked CRC
+    first_shard: int | None = None    # index of the first shard with a bad record; None = clean
+    first_record: int | None = None   # its lowest bad record
+    # (index, TfRecordResult) of every shard that is not clean, in index order; None with per_shard=False
+    shards: tuple | None = ()
+
+    @property
+    def ok(self) -> bool:
+        return self.bad_records == 0
+
+    @classmethod
+    def _of(cls, r, shards=()) -> "TfRecordResult":
+        none = 2**64 - 1
+        fs, fr = int(r.first_shard), int(r.first_record)
+        return cls(int(r.records), int(r.bad_records), int(r.bad_length), int(r.bad_length_crc), int(r.bad_data_crc),
+                   None if fs == none else fs, None if fr == none else fr, shards)
+
+
+def tfrecord_size(records: int, record_size: int) -> int:
+    """Bytes of a framed shard: records * (16 + record_size); ValueError when that overflows 64 bits."""
+    out = _lib.c_u64(0)
+    call("s3dg_tfrecord_size", int(records), int(record_size), ctypes.byref(out))
+    return int(out.value)
+
+
+def _tfr_shards(shards):
+    """(s3dg_tfrecord_shard array, n, bytes of src, dst and index the shards reach)."""
+    rows = []
+    for sh in shards:
+        sh = tuple(int(x) for x in sh)
+        if len(sh) not in (4, 5):
+            raise ValueError("a shard is (src_off, dst_off, records, record_size[, idx_off])")
+        if any(x < 0 or x >= 2**64 for x in sh):
+            raise ValueError("shard fields must fit 64 unsigned bits")
+        rows.append(sh)
+    arr = (_lib.TfrShard * max(1, len(rows)))()
+    need_src = need_dst = need_idx = 0
+    for k, sh in enumerate(rows):
+        src_off, dst_off, records, rs = sh[:4]
+        idx_off = sh[4] if len(sh) == 5 else 0
+        arr[k] = _lib.TfrShard(src_off, dst_off, idx_off, records, rs)
+        if records:
+            need_src = max(need_src, src_off + records * rs)
+            need_dst = max(need_dst, dst_off + records * (16 + rs))
+            need_idx = max(need_idx, idx_off + 16 * records)
+    return arr, len(rows), need_src, need_dst, need_idx
+
+
 _CHUNKS_TIME_PASSES, _CHUNKS_GEAR_TABLE = 1, 2   # S3DG_CHUNKS_* options
 
 
@@ -801,6 +858,38 @@ class Context:
             raise ValueError(f"out holds {int(out.numel())} elements, the batch has {n} objects")
         call("s3dg_crc32_batch_async", self._h, p, arr, n, self._s(stream), self._dst(out, 4 * n))
         return None
+
+    # -- TFRecord shards framed and checked in HBM --------------------------------
+    def tfrecord_frame_batch(self, src, dst, shards, index=None, stream=None) -> None:
+        """Frames every shard of the list in one device call.  Each shard is
+        (src_off, dst_off, records, record_size[, idx_off]): records *
+        record_size payload bytes at src + src_off become the stream
+        build_tfrecord(records, record_size, payload) at dst + dst_off, and,
+        with `index`, 16 bytes per record <offset, length> at index + idx_off.
+        Offsets are multiples of 16; shards may come in any order, be empty
+        and share a source; streams must not overlap each other or a source.
+        The spans are checked against the tensors' sizes before any launch
+        (ValueError).  Ordered on `stream`; returns without waiting."""
+        arr, n, need_src, need_dst, need_idx = _tfr_shards(shards)
+        p_idx = None if index is None else self._dst(index, need_idx)
+        call("s3dg_tfrecord_frame_batch", self._h, self._src(src, need_src), self._dst(dst, need_dst), p_idx, arr, n,
+             self._s(stream))
+
+    def tfrecord_check_batch(self, src, shards, stream=None, per_shard: bool = True) -> TfRecordResult:
+        """The read-side twin of tfrecord_frame_batch over the same shards, of
+        which dst_off, records and record_size are used: the stream of a
+        shard is at src + dst_off.  Per record the length field, the length
+        CRC and the data's CRC against the footer.  Synchronous on `stream`;
+        writes nothing.  per_shard=False asks for the totals only."""
+        arr, n, _, need, _ = _tfr_shards(shards)
+        tot = _lib.TfrRec()
+        per = (_lib.TfrRec * max(1, n))() if per_shard else None
+        call("s3dg_tfrecord_check_batch", self._h, self._src(src, need), arr, n, self._s(stream), ctypes.byref(tot), per)
+        bad = None
+        if per_shard:
+            bad = tuple((k, TfRecordResult._of(per[k], None)) for k in range(n) if per[k].bad_records) \
+                if tot.bad_records else ()
+        return TfRecordResult._of(tot, bad)
 
     def write_ceiling(self, dst, nbytes: int | None = None, pattern: int = 0xA5A5A5A5,
                       stream=None) -> None:
