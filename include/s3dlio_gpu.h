@@ -823,6 +823,72 @@ int s3dg_tfrecord_frame_batch(s3dg_ctx *ctx, const void *src_base, void *dst_bas
  * first_shard being k or UINT64_MAX.  Refusals as above, and "null output". */
 int s3dg_tfrecord_check_batch(s3dg_ctx *ctx, const void *base, const s3dg_tfrecord_shard *shards, uint64_t n,
                               void *stream, s3dg_tfrecord_result *total, s3dg_tfrecord_result *per_shard);
+/* ---- TFRecord shards of records of any length ----
+ * Shard k is `records` records of lengths[len0 .. len0 + records) payload
+ * bytes, packed back to back in the source.  With P_i the sum of the lengths
+ * before record i, the record is framed at dst_off + P_i + 16 i and its index
+ * entry is <u64 P_i + 16 i, u64 16 + len_i>: stream and index are
+ * byte-identical to write_raw_record applied record by record
+ * (src/data_formats/tfrecord.rs:14-75), and to s3dg_tfrecord_frame_batch for a
+ * list of equal lengths.  A length of 0 is a valid 16-byte record. */
+typedef struct {
+    uint64_t src_off;   /* frame: the shard's payload, records packed back to back, at src_base + src_off */
+    uint64_t dst_off;   /* the framed stream at dst_base + dst_off (check: base + dst_off) */
+    uint64_t idx_off;   /* frame: 16 bytes per record at idx_base + idx_off (unused when idx_base is NULL) */
+    uint64_t records;
+    uint64_t len0;      /* the shard's first length: lengths[len0 .. len0 + records) */
+} s3dg_tfrecord_var_shard;
+/* sum(16 + len) over `records` lengths; S3DG_EINVAL when that overflows, when
+ * out is null, or when lengths is null with records present. */
+int s3dg_tfrecord_var_size(const uint64_t *lengths, uint64_t records, uint64_t *out);
+/* s3dg_tfrecord_frame_batch's contract over such shards: ordered on `stream`,
+ * no wait; `shards` and `lengths` (a host array of nlengths) are consumed
+ * before it returns.  Shards may come in any order, be empty and share a
+ * source.  Writes exactly the bytes of each stream and each index.
+ * Refusals: s3dg_tfrecord_frame_batch's, and "null lengths array" with records
+ * present, per shard len0 + records beyond nlengths, a record longer than
+ * 2^31 x 4096, more than 2^46 framed bytes in one call (which a sum that
+ * would overflow exceeds first). */
+int s3dg_tfrecord_frame_var_batch(s3dg_ctx *ctx, const void *src_base, void *dst_base, void *idx_base,
+                                  const s3dg_tfrecord_var_shard *shards, uint64_t n, const uint64_t *lengths,
+                                  uint64_t nlengths, void *stream);
+/* s3dg_tfrecord_check_batch's contract over such shards (dst_off, records and
+ * len0 are used): synchronous, writes nothing to the streams, a clean stream
+ * costs no store and no atomic.  bad_length: the stream's length field
+ * differs from the given length. */
+int s3dg_tfrecord_check_var_batch(s3dg_ctx *ctx, const void *base, const s3dg_tfrecord_var_shard *shards, uint64_t n,
+                                  const uint64_t *lengths, uint64_t nlengths, void *stream, s3dg_tfrecord_result *total,
+                                  s3dg_tfrecord_result *per_shard);
+/* The index of a framed stream nobody has described: index_entries_from_bytes
+ * (src/tfrecord_index.rs:34-80) on the device, for every stream of a list in
+ * one call.  Stream k is `bytes` bytes at base + off (any byte offset); its
+ * entries <u64 offset from the stream's start, u64 16 + len>, at most
+ * max_records of them, go to idx_base + idx_off (a multiple of 16).  The walk
+ * stops silently when fewer than 12 bytes are left (status 0), at a record
+ * whose 12 + len + 4 bytes do not fit (status 1, stop_offset at that record's
+ * start, the entries before it kept), or when max_records entries are written
+ * and 12 or more bytes are left (status 2); resume such a walk at off +
+ * stop_offset.  The length CRC never changes the index; mismatches are
+ * counted beside it. */
+typedef struct {
+    uint64_t off, bytes, idx_off, max_records;
+} s3dg_tfrecord_stream;
+typedef struct {
+    uint64_t records;          /* complete records found; their entries are written */
+    uint64_t status;           /* 0 complete, 1 truncated record, 2 max_records reached */
+    uint64_t stop_offset;      /* offset in the stream of the first byte not covered by an entry */
+    uint64_t trailing;         /* bytes - stop_offset */
+    uint64_t bad_length_crc;   /* records whose length CRC is not masked_crc of their 8 length bytes */
+    uint64_t first_bad_record; /* the lowest such record; UINT64_MAX when none */
+} s3dg_tfrecord_walk_result;
+/* Synchronous on `stream`; results is a host array of n.  One wave follows one
+ * stream's chain of length fields.  Refusals (S3DG_EINVAL, before anything is
+ * reserved or enqueued): "null context", "null base", "null idx_base", "null
+ * results", "null stream array", a misaligned idx_base, more than 2^32 - 1
+ * streams, and per stream ("stream k: ...") idx_off no multiple of 16 or an
+ * end address overflowing.  n == 0 succeeds whatever the other pointers. */
+int s3dg_tfrecord_index_batch(s3dg_ctx *ctx, const void *base, void *idx_base, const s3dg_tfrecord_stream *streams,
+                              uint64_t n, void *stream, s3dg_tfrecord_walk_result *results);
 /* zlib crc32_combine: CRC of A||B from crc(A), crc(B), |B| (host). */
 uint32_t s3dg_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2);
 /* Host CRC-32 update (crc32fast::Hasher semantics: start from 0). */

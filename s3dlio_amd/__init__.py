@@ -8,8 +8,9 @@ the library is absent (no CPU fallback exists).
 from ._lib import S3dgError, lib  # noqa: F401  (loads libs3dlio_amd.so)
 from .hostbuf import BytesView  # noqa: F401
 from .device import (BLOCK_SIZE, DEFAULT_BASE_SEED, BatchVerifyResult, ChunkResult, Chunker, Context, LzMeasure,  # noqa: F401
-                     LzResult, Measure, MeasureResult, TfRecordResult, VerifyResult, compress_ratio, device_count,
-                     host_context, host_slots, object_entropy, parse_devices, tfrecord_size, unique_blocks, xoshiro_jump)
+                     LzResult, Measure, MeasureResult, TfRecordResult, TfRecordWalk, VerifyResult, compress_ratio,
+                     device_count, host_context, host_slots, object_entropy, parse_devices, tfrecord_index_text,
+                     tfrecord_size, tfrecord_var_size, unique_blocks, xoshiro_jump)
 from .data_gen import (HostRegistration, fill_controlled_data, fill_controlled_data_seeded,  # noqa: F401
                        measure_chunks_data, measure_data, measure_lz_data, register_host_buffer, unregister_host_buffer,
                        verify_controlled_data_seeded, verify_generated_data)

@@ -70,6 +70,22 @@ class TfrRec(ctypes.Structure):
                 ("bad_data_crc", c_u64), ("first_shard", c_u64), ("first_record", c_u64)]
 
 
+class TfrVarShard(ctypes.Structure):
+    """s3dg_tfrecord_var_shard"""
+    _fields_ = [("src_off", c_u64), ("dst_off", c_u64), ("idx_off", c_u64), ("records", c_u64), ("len0", c_u64)]
+
+
+class TfrStream(ctypes.Structure):
+    """s3dg_tfrecord_stream"""
+    _fields_ = [("off", c_u64), ("bytes", c_u64), ("idx_off", c_u64), ("max_records", c_u64)]
+
+
+class TfrWalkRec(ctypes.Structure):
+    """s3dg_tfrecord_walk_result"""
+    _fields_ = [("records", c_u64), ("status", c_u64), ("stop_offset", c_u64), ("trailing", c_u64),
+                ("bad_length_crc", c_u64), ("first_bad_record", c_u64)]
+
+
 class MeasureRec(ctypes.Structure):
     """s3dg_measure_result"""
     _fields_ = [("bytes", c_u64), ("zero_bytes", c_u64), ("blocks", c_u64), ("unique_blocks", c_u64),
@@ -204,6 +220,13 @@ SIGNATURES = {
     "s3dg_tfrecord_frame_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(TfrShard), c_u64, c_vp]),
     "s3dg_tfrecord_check_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(TfrShard), c_u64, c_vp,
                                           ctypes.POINTER(TfrRec), ctypes.POINTER(TfrRec)]),
+    "s3dg_tfrecord_var_size": (c_int, [ctypes.POINTER(c_u64), c_u64, ctypes.POINTER(c_u64)]),
+    "s3dg_tfrecord_frame_var_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(TfrVarShard), c_u64,
+                                              ctypes.POINTER(c_u64), c_u64, c_vp]),
+    "s3dg_tfrecord_check_var_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(TfrVarShard), c_u64, ctypes.POINTER(c_u64), c_u64,
+                                              c_vp, ctypes.POINTER(TfrRec), ctypes.POINTER(TfrRec)]),
+    "s3dg_tfrecord_index_batch": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(TfrStream), c_u64, c_vp,
+                                          ctypes.POINTER(TfrWalkRec)]),
     "s3dg_crc32_combine": (c_u32, [c_u32, c_u32, c_u64]),
     "s3dg_crc32_host": (c_u32, [c_u32, c_vp, c_u64]),
     "s3dg_npz_size": (c_int, [ctypes.POINTER(c_u64), c_int, ctypes.c_char_p, c_u64,

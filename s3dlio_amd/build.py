@@ -31,7 +31,8 @@ SOURCES = [os.path.join(CSRC, "s3dg_ks_kernels.hip"), os.path.join(CSRC, "s3dg_b
            os.path.join(CSRC, "s3dg_chunks.cpp"), os.path.join(CSRC, "s3dg_lz.hip"),
            os.path.join(CSRC, "s3dg_lz.cpp"), os.path.join(CSRC, "s3dg_verify_batch.cpp"),
            os.path.join(CSRC, "s3dg_dgen_batch.cpp"), os.path.join(CSRC, "s3dg_crc_batch.cpp"),
-           os.path.join(CSRC, "s3dg_tfrecord.hip"), os.path.join(CSRC, "s3dg_tfrecord.cpp")]
+           os.path.join(CSRC, "s3dg_tfrecord.hip"), os.path.join(CSRC, "s3dg_tfrecord.cpp"),
+           os.path.join(CSRC, "s3dg_tfrecord_var.hip"), os.path.join(CSRC, "s3dg_tfrecord_var.cpp")]
 HEADERS = [os.path.join(CSRC, "s3dg_internal.h"), os.path.join(CSRC, "s3dg_dev.h"),
            os.path.join(CSRC, "s3dg_ctx.h"),
            os.path.join(CSRC, "s3dg_batch_plan.h"), os.path.join(CSRC, "s3dg_ks_verify_plan.h"),
@@ -43,7 +44,7 @@ HEADERS = [os.path.join(CSRC, "s3dg_internal.h"), os.path.join(CSRC, "s3dg_dev.h
            os.path.join(CSRC, "s3dg_span_batch_plan.h"),
            os.path.join(CSRC, "s3dg_accum.h"), os.path.join(CSRC, "s3dg_dgen_batch_plan.h"),
            os.path.join(CSRC, "s3dg_ks_plan.h"), os.path.join(CSRC, "s3dg_crc_batch_plan.h"),
-           os.path.join(CSRC, "s3dg_tfrecord_plan.h"),
+           os.path.join(CSRC, "s3dg_tfrecord_plan.h"), os.path.join(CSRC, "s3dg_tfrecord_var_plan.h"),
            os.path.join(CSRC, "s3dg_prefix.h"),
            os.path.join(ROOT, "include", "s3dlio_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -13,6 +13,7 @@
 #include "s3dg_ks_plan.h"           // the uniform keystream launches' plan, fastmod
 #include "s3dg_crc_batch_plan.h"    // CrcBatchCounts, the batch CRC's table
 #include "s3dg_tfrecord_plan.h"     // TfrCounts, the TFRecord calls' table
+#include "s3dg_tfrecord_var_plan.h" // TfvCounts, the per-record table
 #include "s3dg_prefix.h"            // PrefixParams and the one function that makes them
 
 // Sets the calling thread's error text (s3dg_last_error) and returns code.
@@ -388,6 +389,17 @@ struct TfrDevRes {
 // the regions and, when the call has long records, one thread per such record.
 hipError_t tfrecord_launch(bool frame, const uint8_t *src, uint8_t *dst, uint8_t *idx, const uint8_t *table_dev,
                            const TfrCounts &C, void *tab_dev, int cus, TfrDevRes *res, hipStream_t s);
+// Shards of records of any length (s3dg_tfrecord_var.hip; s3dg_tfrecord_var_plan.h):
+// table_dev is the uploaded table of tfv_build with room for the records'
+// constants and the regions' raw CRCs behind it (tfv_device_bytes).  One launch
+// for the constants, one over the regions and, when the call has long records,
+// one thread per such record.
+hipError_t tfrecord_var_launch(bool frame, const uint8_t *src, uint8_t *dst, uint8_t *idx, const uint8_t *table_dev,
+                               const TfvCounts &C, void *tab_dev, int cus, TfrDevRes *res, hipStream_t s);
+// One wave per stream of streams_dev[0, n) follows its length fields from
+// base + off, stores its entries at idx + idx_off and its result at res_dev[k].
+hipError_t tfrecord_walk_launch(const uint8_t *base, uint8_t *idx, const s3dg_tfrecord_stream *streams_dev, uint64_t n,
+                                s3dg_tfrecord_walk_result *res_dev, int cus, hipStream_t s);
 
 // ---- NUMA placement of host buffers (s3dg_numa.cpp) -------------------------
 bool device_local_cpus(int device, cpu_set_t *out);

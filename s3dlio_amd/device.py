@@ -258,6 +258,96 @@ def _tfr_shards(shards):
     return arr, len(rows), need_src, need_dst, need_idx
 
 
+_WALK_STATUS = ("complete", "truncated", "full")
+
+
+@dataclass(frozen=True)
+class TfRecordWalk:
+    """What Context.tfrecord_index_batch found in one stream
+    (s3dg_tfrecord_walk_result)."""
+    records: int = 0              # complete records found; their entries are written
+    status: str = "complete"      # "complete" | "truncated" (a record does not fit) | "full" (max_records reached)
+    stop_offset: int = 0          # offset in the stream of the first byte not covered by an entry
+    trailing: int = 0             # bytes - stop_offset
+    bad_length_crc: int = 0       # records whose length CRC is not masked_crc of their 8 length bytes
+    first_bad_record: int | None = None   # the lowest such record
+
+    @property
+    def ok(self) -> bool:
+        return self.status == "complete" and self.bad_length_crc == 0
+
+    @classmethod
+    def _of(cls, r) -> "TfRecordWalk":
+        fb = int(r.first_bad_record)
+        return cls(int(r.records), _WALK_STATUS[int(r.status)], int(r.stop_offset), int(r.trailing),
+                   int(r.bad_length_crc), None if fb == 2**64 - 1 else fb)
+
+
+def _tfr_lengths(lengths) -> np.ndarray:
+    """Any integer sequence or numpy array as a contiguous uint64 array."""
+    if isinstance(lengths, np.ndarray):
+        a = lengths
+        if a.size == 0:
+            return np.zeros(0, np.uint64)
+        if a.ndim != 1:
+            raise ValueError("lengths must be one-dimensional")
+        if a.dtype.kind not in "iu":
+            raise ValueError("lengths must be integers")
+        if a.dtype.kind == "i" and int(a.min()) < 0:
+            raise ValueError("lengths must fit 64 unsigned bits")
+        return np.ascontiguousarray(a, dtype=np.uint64)
+    vals = list(lengths)   # Python integers above 2^63 would make numpy guess a float array
+    if not all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in vals):
+        raise ValueError("lengths must be integers")
+    if any(x < 0 or x >= 2**64 for x in vals):
+        raise ValueError("lengths must fit 64 unsigned bits")
+    return np.array([int(x) for x in vals], dtype=np.uint64)
+
+
+def tfrecord_var_size(lengths) -> int:
+    """Bytes of a framed shard of records of these lengths: sum(16 + length);
+    ValueError when that overflows 64 bits."""
+    a = _tfr_lengths(lengths)
+    out = _lib.c_u64(0)
+    call("s3dg_tfrecord_var_size", a.ctypes.data_as(ctypes.POINTER(_lib.c_u64)), len(a), ctypes.byref(out))
+    return int(out.value)
+
+
+def tfrecord_index_text(entries) -> str:
+    """The DALI text form of an index, "{offset} {size}\\n" per record
+    (index_text_from_bytes, src/tfrecord_index.rs:92-101): entries is an (n, 2)
+    array or an iterable of (offset, size)."""
+    return "".join(f"{int(o)} {int(s)}\n" for o, s in np.asarray(entries, dtype=np.uint64).reshape(-1, 2).tolist())
+
+
+def _tfr_var_shards(shards):
+    """(s3dg_tfrecord_var_shard array, n, the concatenated lengths, bytes of
+    src, dst and index the shards reach)."""
+    rows, lens = [], []
+    for sh in shards:
+        if len(sh) not in (3, 4):
+            raise ValueError("a shard is (src_off, dst_off, lengths[, idx_off])")
+        offs = [int(sh[0]), int(sh[1]), int(sh[3]) if len(sh) == 4 else 0]
+        if any(x < 0 or x >= 2**64 for x in offs):
+            raise ValueError("shard fields must fit 64 unsigned bits")
+        rows.append(offs)
+        lens.append(_tfr_lengths(sh[2]))
+    arr = (_lib.TfrVarShard * max(1, len(rows)))()
+    need_src = need_dst = need_idx = 0
+    len0 = 0
+    for k, ((src_off, dst_off, idx_off), a) in enumerate(zip(rows, lens)):
+        records = len(a)
+        arr[k] = _lib.TfrVarShard(src_off, dst_off, idx_off, records, len0)
+        len0 += records
+        if records:
+            payload = sum(a.tolist()) if a.max() >= 2**40 else int(a.sum())
+            need_src = max(need_src, src_off + payload)
+            need_dst = max(need_dst, dst_off + payload + 16 * records)
+            need_idx = max(need_idx, idx_off + 16 * records)
+    cat = np.concatenate(lens) if lens else np.zeros(0, np.uint64)
+    return arr, len(rows), np.ascontiguousarray(cat, dtype=np.uint64), need_src, need_dst, need_idx
+
+
 _CHUNKS_TIME_PASSES, _CHUNKS_GEAR_TABLE = 1, 2   # S3DG_CHUNKS_* options
 
 
@@ -890,6 +980,88 @@ class Context:
             bad = tuple((k, TfRecordResult._of(per[k], None)) for k in range(n) if per[k].bad_records) \
                 if tot.bad_records else ()
         return TfRecordResult._of(tot, bad)
+
+    # -- TFRecord shards of records of any length; streams nobody has described -----
+    def tfrecord_frame_var_batch(self, src, dst, shards, index=None, stream=None) -> None:
+        """tfrecord_frame_batch for records of any length.  Each shard is
+        (src_off, dst_off, lengths[, idx_off]): lengths (any integer sequence
+        or numpy array) are the payload bytes of its records, packed back to
+        back at src + src_off; record i is framed at dst + dst_off + P_i + 16 i
+        (P_i: the lengths before it) and, with `index`, its entry
+        <P_i + 16 i, 16 + len_i> is at index + idx_off + 16 i.  Offsets are
+        multiples of 16; shards may come in any order, be empty and share a
+        source.  The spans are checked against the tensors' sizes before any
+        launch (ValueError).  Ordered on `stream`; returns without waiting."""
+        arr, n, lens, need_src, need_dst, need_idx = _tfr_var_shards(shards)
+        p_idx = None if index is None else self._dst(index, need_idx)
+        call("s3dg_tfrecord_frame_var_batch", self._h, self._src(src, need_src), self._dst(dst, need_dst), p_idx, arr, n,
+             lens.ctypes.data_as(ctypes.POINTER(_lib.c_u64)), len(lens), self._s(stream))
+
+    def tfrecord_check_var_batch(self, src, shards, stream=None, per_shard: bool = True) -> TfRecordResult:
+        """The read-side twin of tfrecord_frame_var_batch over the same shards,
+        of which dst_off and lengths are used: the stream of a shard is at
+        src + dst_off.  Per record the length field against the given length,
+        the length CRC and the data's CRC against the footer.  Synchronous on
+        `stream`; writes nothing.  per_shard=False asks for the totals only."""
+        arr, n, lens, _, need, _ = _tfr_var_shards(shards)
+        tot = _lib.TfrRec()
+        per = (_lib.TfrRec * max(1, n))() if per_shard else None
+        call("s3dg_tfrecord_check_var_batch", self._h, self._src(src, need), arr, n,
+             lens.ctypes.data_as(ctypes.POINTER(_lib.c_u64)), len(lens), self._s(stream), ctypes.byref(tot), per)
+        bad = None
+        if per_shard:
+            bad = tuple((k, TfRecordResult._of(per[k], None)) for k in range(n) if per[k].bad_records) \
+                if tot.bad_records else ()
+        return TfRecordResult._of(tot, bad)
+
+    def tfrecord_index_batch(self, src, streams, index, stream=None) -> list:
+        """The index of framed streams nobody has described, in one device
+        call: each stream is (off, nbytes, idx_off, max_records), nbytes at
+        src + off (any byte offset), and gets its entries <offset from the
+        stream's start, 16 + len>, at most max_records of them, at
+        index + idx_off (a multiple of 16).  index_entries_from_bytes'
+        semantics: fewer than 12 bytes left end the walk silently, a record
+        that does not fit ends it as "truncated" with the entries before it
+        kept; "full" means max_records entries are written and more follows
+        (resume at off + stop_offset).  Synchronous on `stream`.  Returns a
+        TfRecordWalk per stream."""
+        rows = [tuple(int(x) for x in st) for st in streams]
+        if any(len(st) != 4 for st in rows):
+            raise ValueError("a stream is (off, nbytes, idx_off, max_records)")
+        if any(x < 0 or x >= 2**64 for st in rows for x in st):
+            raise ValueError("stream fields must fit 64 unsigned bits")
+        n = len(rows)
+        arr = (_lib.TfrStream * max(1, n))()
+        need_src = need_idx = 0
+        for k, (off, nbytes, idx_off, cap) in enumerate(rows):
+            arr[k] = _lib.TfrStream(off, nbytes, idx_off, cap)
+            need_src = max(need_src, off + nbytes)
+            need_idx = max(need_idx, idx_off + 16 * min(cap, nbytes // 16))
+        res = (_lib.TfrWalkRec * max(1, n))()
+        call("s3dg_tfrecord_index_batch", self._h, self._src(src, need_src), self._dst(index, need_idx), arr, n,
+             self._s(stream), res)
+        return [TfRecordWalk._of(res[k]) for k in range(n)]
+
+    def tfrecord_scan(self, src, streams, stream=None):
+        """"I only have bytes": streams is an iterable of (off, nbytes) with
+        off a multiple of 16.  Walks every stream (tfrecord_index_batch with
+        room for every record the bytes could hold), copies the entries back,
+        and checks the records found (tfrecord_check_var_batch with lengths
+        size - 16).  Returns (walks, index arrays, TfRecordResult): one
+        TfRecordWalk and one uint64 array of shape (records, 2) per stream."""
+        t = _lib.torch
+        spans = [(int(off), int(nbytes)) for off, nbytes in streams]
+        idx_off, at = [], 0
+        for _, nbytes in spans:
+            idx_off.append(at)
+            at += 16 * (nbytes // 16)
+        index = t.empty(max(16, at), dtype=t.uint8, device=f"cuda:{self.device}")
+        walks = self.tfrecord_index_batch(src, [(off, nbytes, io, nbytes // 16) for (off, nbytes), io in zip(spans, idx_off)],
+                                          index, stream=stream)
+        host = index.cpu().numpy()
+        entries = [host[io:io + 16 * w.records].view("<u8").reshape(-1, 2).astype(np.uint64) for io, w in zip(idx_off, walks)]
+        shards = [(0, off, e[:, 1] - np.uint64(16)) for (off, _), e in zip(spans, entries)]
+        return walks, entries, self.tfrecord_check_var_batch(src, shards, stream=stream)
 
     def write_ceiling(self, dst, nbytes: int | None = None, pattern: int = 0xA5A5A5A5,
                       stream=None) -> None:
