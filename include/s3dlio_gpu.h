@@ -696,6 +696,12 @@ int s3dg_host_free_pinned(void *p);
  * (1 MiB: ~33 us against ~57 us through the bounce path).  Registrations that
  * overlap the range are dropped first; registering the same range again is a
  * no-op.  0 or a negative S3DG_E* status.
+ * Where the platform cannot page-lock memory a process already has
+ * (hipHostRegister fails on a page of the library's own as well, as on a GPU
+ * passed through to a virtual machine), the range is recorded without a GPU
+ * mapping and the call returns 0: calls inside it are exact and take the same
+ * paths as for any pageable buffer, s3dg_host_unregister counts it, and only
+ * the speed-up is absent (s3dg_host_alloc_pinned memory has it everywhere).
  * CONTRACT (hipHostRegister's): the buffer stays allocated until
  * s3dg_host_unregister.  Unmapped while registered, its GPU mapping goes with
  * its pages and the next call into it is a GPU memory fault.  The bindings

@@ -33,11 +33,15 @@
 // benches/performance_microbenchmarks.rs:43-64 reuses one buffer).  The
 // buffer must stay allocated until s3dg_host_unregister(buf) (the bindings
 // hold it: s3dlio_amd.register_host_buffer, HostRegistration in the Rust
-// patch).
+// patch).  Where the platform cannot page-lock memory a process already has
+// (hipHostRegister fails on a page of the library's own too: GPUs passed
+// through to a virtual machine), a registration is recorded without a GPU
+// mapping and calls inside it take the regular paths.
 #include "s3dg_internal.h"
 #include "s3dg_span_plan.h"
 #include "s3dlio_gpu.h"
 
+#include <sys/mman.h>
 #include <sys/random.h>
 #include <time.h>
 
@@ -461,7 +465,7 @@ int host_launch_blocks(HostStaging *sg, const HostJob &J, uint8_t *dst, uint64_t
 namespace {
 struct UserReg {
     uint64_t bytes;    // page-rounded length
-    uint8_t *dev;      // device pointer of the first page
+    uint8_t *dev;      // device pointer of the first page; nullptr: recorded only (host_register_works)
     int users;         // host calls in flight on it (they hold it until they return)
 };
 struct UserRegs {
@@ -488,8 +492,10 @@ int drop_regs(UserRegs &R, std::unique_lock<std::mutex> &g, Hit hit) {
                 busy = true;
                 ++q;
             } else {
-                (void)hipHostUnregister((void *)q->first);
-                (void)hipGetLastError();
+                if (q->second.dev) {
+                    (void)hipHostUnregister((void *)q->first);
+                    (void)hipGetLastError();
+                }
                 q = R.regs.erase(q);
                 ++dropped;
             }
@@ -533,12 +539,34 @@ uint8_t *user_registered(const uint8_t *p, uint64_t n, bool direct_ok, UserHold 
             // copy into it must not see the pages unregistered mid-flight)
             ++it->second.users;
             hold.key = it->first;
-            return direct_ok ? it->second.dev + (a - it->first) : nullptr;
+            return direct_ok && it->second.dev ? it->second.dev + (a - it->first) : nullptr;
         }
     }
     const uintptr_t lo = a & ~(uintptr_t)4095, hi = (a + n + 4095) & ~(uintptr_t)4095;
     drop_regs(R, g, [&](uintptr_t s0, uint64_t len) { return s0 < hi && s0 + len > lo; });
     return nullptr;
+}
+
+// Whether hipHostRegister can page-lock existing memory here at all, asked
+// once, after a caller's registration failed: a touched page of the library's
+// own is registered and released.  True without a visible GPU (the caller's
+// error stands).
+bool host_register_works() {
+    static const bool works = [] {
+        int ndev = 0;
+        const bool gpu = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
+        (void)hipGetLastError();
+        if (!gpu) return true;
+        void *pg = mmap(nullptr, 4096, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+        if (pg == MAP_FAILED) return true;
+        memset(pg, 0, 4096);
+        const hipError_t e = hipHostRegister(pg, 4096, hipHostRegisterPortable | hipHostRegisterMapped);
+        if (e == hipSuccess) (void)hipHostUnregister(pg);
+        (void)hipGetLastError();
+        munmap(pg, 4096);
+        return e == hipSuccess;
+    }();
+    return works;
 }
 
 }  // namespace
@@ -555,7 +583,14 @@ extern "C" int s3dg_host_register(void *buf, uint64_t len) {
     hipError_t e = hipHostRegister((void *)lo, hi - lo, hipHostRegisterPortable | hipHostRegisterMapped);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return s3dg_internal_fail(S3DG_EHIP, (std::string("hipHostRegister: ") + hipGetErrorString(e)).c_str());
+        if (host_register_works())
+            return s3dg_internal_fail(S3DG_EHIP, (std::string("hipHostRegister: ") + hipGetErrorString(e)).c_str());
+        // no page-locking of existing memory on this platform: the range is
+        // recorded (unregister and the overlap rules see it), and calls inside
+        // it go through the bounce buffer or the copy engine as for any
+        // pageable buffer
+        R.regs[lo] = UserReg{hi - lo, nullptr, 0};
+        return S3DG_OK;
     }
     void *d = nullptr;
     e = hipHostGetDevicePointer(&d, (void *)lo, 0);
