@@ -895,6 +895,32 @@ typedef struct {
  * end address overflowing.  n == 0 succeeds whatever the other pointers. */
 int s3dg_tfrecord_index_batch(s3dg_ctx *ctx, const void *base, void *idx_base, const s3dg_tfrecord_stream *streams,
                               uint64_t n, void *stream, s3dg_tfrecord_walk_result *results);
+/* s3dg_tfrecord_index_batch with parallelism inside a stream: the same
+ * arguments, the same refusals with the same messages, and exactly the same
+ * results and index bytes for every input, wrong length CRCs and truncations
+ * included.  Every position of every stream is tested for a header whose
+ * record fits and whose length CRC is right; the candidates are linked into a
+ * forest, hop tables of hop_records links are built by pointer doubling, and
+ * one wave per stream follows the chain from byte 0 hop by hop (a header whose
+ * CRC is wrong is stepped through from the raw bytes, as the walk does) while
+ * a thread per hop stores the entries.  It reads every byte, so it is the call
+ * for few long streams; s3dg_tfrecord_index_batch, which reads 12 bytes per
+ * record, is the call for many streams (DESIGN.md §5.5.3 has the figures).
+ * Scratch: bytes / 8 + bytes / 32 per stream rounded up to whole tiles of
+ * tile_bytes, and 52 bytes per candidate, kept with the stream's state.
+ * Two more refusals, neither reachable below 2^45 bytes in a call: "more than
+ * 2^31 - 2 search tiles in one call", "more than 2^32 - 16 header candidates
+ * in one call". */
+int s3dg_tfrecord_index_search_batch(s3dg_ctx *ctx, const void *base, void *idx_base, const s3dg_tfrecord_stream *streams,
+                                     uint64_t n, void *stream, s3dg_tfrecord_walk_result *results);
+/* The same call with its passes timed by device events: pass_ms[6] gets the
+ * milliseconds of the candidate pass, the sum over the tiles, the link pass,
+ * the doubling rounds, the anchor walk and the fill ("null pass_ms"). */
+int s3dg_tfrecord_index_search_timed(s3dg_ctx *ctx, const void *base, void *idx_base, const s3dg_tfrecord_stream *streams,
+                                     uint64_t n, void *stream, s3dg_tfrecord_walk_result *results, float *pass_ms);
+/* The search's two constants, for placing test edges: positions per tile and
+ * records per hop, both powers of two.  No context, no device. */
+int s3dg_tfrecord_search_geometry(uint32_t *tile_bytes, uint32_t *hop_records);
 /* zlib crc32_combine: CRC of A||B from crc(A), crc(B), |B| (host). */
 uint32_t s3dg_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2);
 /* Host CRC-32 update (crc32fast::Hasher semantics: start from 0). */

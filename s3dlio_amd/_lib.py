@@ -227,6 +227,11 @@ SIGNATURES = {
                                               c_vp, ctypes.POINTER(TfrRec), ctypes.POINTER(TfrRec)]),
     "s3dg_tfrecord_index_batch": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(TfrStream), c_u64, c_vp,
                                           ctypes.POINTER(TfrWalkRec)]),
+    "s3dg_tfrecord_index_search_batch": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(TfrStream), c_u64, c_vp,
+                                                 ctypes.POINTER(TfrWalkRec)]),
+    "s3dg_tfrecord_index_search_timed": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(TfrStream), c_u64, c_vp,
+                                                 ctypes.POINTER(TfrWalkRec), ctypes.POINTER(ctypes.c_float)]),
+    "s3dg_tfrecord_search_geometry": (c_int, [ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
     "s3dg_crc32_combine": (c_u32, [c_u32, c_u32, c_u64]),
     "s3dg_crc32_host": (c_u32, [c_u32, c_vp, c_u64]),
     "s3dg_npz_size": (c_int, [ctypes.POINTER(c_u64), c_int, ctypes.c_char_p, c_u64,

@@ -14,6 +14,7 @@
 #include "s3dg_crc_batch_plan.h"    // CrcBatchCounts, the batch CRC's table
 #include "s3dg_tfrecord_plan.h"     // TfrCounts, the TFRecord calls' table
 #include "s3dg_tfrecord_var_plan.h" // TfvCounts, the per-record table
+#include "s3dg_tfrecord_search_plan.h" // TfsPlanA, TfsPlanB: the search's workspaces
 #include "s3dg_prefix.h"            // PrefixParams and the one function that makes them
 
 // Sets the calling thread's error text (s3dg_last_error) and returns code.
@@ -400,6 +401,19 @@ hipError_t tfrecord_var_launch(bool frame, const uint8_t *src, uint8_t *dst, uin
 // base + off, stores its entries at idx + idx_off and its result at res_dev[k].
 hipError_t tfrecord_walk_launch(const uint8_t *base, uint8_t *idx, const s3dg_tfrecord_stream *streams_dev, uint64_t n,
                                 s3dg_tfrecord_walk_result *res_dev, int cus, hipStream_t s);
+// The same results with parallelism inside a stream (s3dg_tfrecord_search.hip;
+// s3dg_tfrecord_search_plan.h).  wa is the workspace of tfs_plan_a with the
+// streams and their first tiles uploaded, wb that of tfs_plan_b.  First the
+// candidate pass and the sum over the tiles' counts, which leaves the call's
+// candidates at tbase[tiles]; with that number on the host, the rest.  The
+// events (nullable) are recorded behind the candidate pass and behind the link,
+// the doubling, the anchor walk and the fill.
+hipError_t tfrecord_search_scan(void *tmp, size_t *tmp_bytes, uint64_t *tbase, uint64_t tiles, hipStream_t s);
+hipError_t tfrecord_search_candidates(const uint8_t *base, const uint8_t *wa, const TfsPlanA &A, uint64_t n, uint64_t tiles,
+                                      size_t scan_tmp_bytes, int cus, hipEvent_t searched, hipStream_t s);
+hipError_t tfrecord_search_resolve(const uint8_t *base, uint8_t *idx, const uint8_t *wa, const TfsPlanA &A, uint8_t *wb,
+                                   const TfsPlanB &B, uint64_t n, uint64_t tiles, uint32_t nodes, int cus, hipEvent_t *marks,
+                                   hipStream_t s);
 
 // ---- NUMA placement of host buffers (s3dg_numa.cpp) -------------------------
 bool device_local_cpus(int device, cpu_set_t *out);

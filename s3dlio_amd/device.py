@@ -313,6 +313,15 @@ def tfrecord_var_size(lengths) -> int:
     return int(out.value)
 
 
+def tfrecord_search_geometry() -> tuple[int, int]:
+    """(tile_bytes, hop_records) of Context.tfrecord_index_search_batch: the
+    positions a workgroup of its candidate pass takes and the records one hop
+    of its anchor walk covers, both powers of two.  Needs no device."""
+    tile, hop = _lib.c_u32(0), _lib.c_u32(0)
+    call("s3dg_tfrecord_search_geometry", ctypes.byref(tile), ctypes.byref(hop))
+    return int(tile.value), int(hop.value)
+
+
 def tfrecord_index_text(entries) -> str:
     """The DALI text form of an index, "{offset} {size}\\n" per record
     (index_text_from_bytes, src/tfrecord_index.rs:92-101): entries is an (n, 2)
@@ -1024,7 +1033,26 @@ class Context:
         that does not fit ends it as "truncated" with the entries before it
         kept; "full" means max_records entries are written and more follows
         (resume at off + stop_offset).  Synchronous on `stream`.  Returns a
-        TfRecordWalk per stream."""
+        TfRecordWalk per stream.  One wave follows one stream, 12 bytes read
+        per record: the call for many streams; for a few long ones
+        tfrecord_index_search_batch gives the same answer faster (DESIGN.md
+        §5.5.3 has the figures)."""
+        return self._tfrecord_walks("s3dg_tfrecord_index_batch", src, streams, index, stream)
+
+    def tfrecord_index_search_batch(self, src, streams, index, stream=None) -> list:
+        """tfrecord_index_batch with parallelism inside a stream: the same
+        arguments and exactly the same result and index bytes for every
+        input.  Every position is tested for a fitting header with a right
+        length CRC, the candidates are linked and the chain from byte 0 is
+        resolved tfrecord_search_geometry()[1] records a hop; headers with a
+        wrong CRC are stepped through one by one, as the walk does.  It reads
+        every byte: the call for few long streams, where tfrecord_index_batch
+        waits on one load per record; with many streams in a call that one is
+        faster (DESIGN.md §5.5.3 has the figures).  Scratch of about a fifth
+        of the streams' bytes is kept with the stream's state."""
+        return self._tfrecord_walks("s3dg_tfrecord_index_search_batch", src, streams, index, stream)
+
+    def _tfrecord_walks(self, sym, src, streams, index, stream) -> list:
         rows = [tuple(int(x) for x in st) for st in streams]
         if any(len(st) != 4 for st in rows):
             raise ValueError("a stream is (off, nbytes, idx_off, max_records)")
@@ -1038,8 +1066,7 @@ class Context:
             need_src = max(need_src, off + nbytes)
             need_idx = max(need_idx, idx_off + 16 * min(cap, nbytes // 16))
         res = (_lib.TfrWalkRec * max(1, n))()
-        call("s3dg_tfrecord_index_batch", self._h, self._src(src, need_src), self._dst(index, need_idx), arr, n,
-             self._s(stream), res)
+        call(sym, self._h, self._src(src, need_src), self._dst(index, need_idx), arr, n, self._s(stream), res)
         return [TfRecordWalk._of(res[k]) for k in range(n)]
 
     def tfrecord_scan(self, src, streams, stream=None):
