@@ -589,10 +589,25 @@ int s3dg_chunks_get(s3dg_chunks *h, s3dg_chunk_result *out);
  * the latest such add and writes its candidate, cut and fingerprint pass times
  * to seconds[0..2].  S3DG_CHUNKS_GEAR_TABLE (0 / 1, default 1): the candidate
  * pass reads G from 256 words of LDS or computes it per byte; results are
- * identical. */
-enum { S3DG_CHUNKS_TIME_PASSES = 1, S3DG_CHUNKS_GEAR_TABLE = 2 };
+ * identical.
+ *
+ * S3DG_CHUNKS_SEARCH_WALK (bytes, default 0 = off; negative: refused): in the
+ * following adds (stream and batch form, per object) every object of at least
+ * this many bytes has its cuts walked in parallel inside the object (DESIGN.md
+ * 5.11.1) instead of by one wave; smaller objects of the same add keep the
+ * wave.  Every field of the result is the same either way, for every input;
+ * the adds stay asynchronous.  It pays for large single objects (the wave
+ * takes about a microsecond per chunk of an object, one after the other) and
+ * costs scratch: s3dg_chunks_search_geometry reports node_bytes per node and
+ * hop_links, the links one step of the remaining serial part covers; an
+ * object reserves ceil(len / min_bytes) + 1 + 2 ceil(len / avg_bytes) + 64
+ * nodes.  An object with more candidates than that is walked by the wave,
+ * decided on the device.  seconds[1] of s3dg_chunks_pass_seconds covers
+ * everything that replaces the walk. */
+enum { S3DG_CHUNKS_TIME_PASSES = 1, S3DG_CHUNKS_GEAR_TABLE = 2, S3DG_CHUNKS_SEARCH_WALK = 4 };
 int s3dg_chunks_set_option(s3dg_chunks *h, int option, int value);
 int s3dg_chunks_pass_seconds(s3dg_chunks *h, double *seconds);
+int s3dg_chunks_search_geometry(uint32_t *hop_links, uint32_t *node_bytes);   /* needs no device */
 /* A host buffer (any alignment, read-only memory included) as one object, on
  * a host slot's GPU.  Windows and chunks cross any copy's edge, so the whole
  * buffer is staged in device memory (len rounded up to 16 bytes, copied 64 MiB

@@ -174,6 +174,7 @@ SIGNATURES = {
     "s3dg_chunks_get": (c_int, [c_vp, ctypes.POINTER(ChunkRec)]),
     "s3dg_chunks_set_option": (c_int, [c_vp, c_int, c_int]),
     "s3dg_chunks_pass_seconds": (c_int, [c_vp, ctypes.POINTER(ctypes.c_double)]),
+    "s3dg_chunks_search_geometry": (c_int, [ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
     "s3dg_chunk_data": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, ctypes.POINTER(ChunkRec)]),
     "s3dg_lz_create": (c_int, [c_vp, c_u64, ctypes.POINTER(c_vp)]),
     "s3dg_lz_destroy": (c_int, [c_vp]),

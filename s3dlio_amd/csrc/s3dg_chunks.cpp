@@ -27,6 +27,7 @@ struct s3dg_chunks : Accum<ChunkStream> {
     uint64_t work_cap = 0;
     bool table = true;                 // pass A reads the gear values from LDS
     bool timing = false;
+    uint64_t search_min = 0;           // S3DG_CHUNKS_SEARCH_WALK: objects from this size on take the parallel walk
     ChunkStream *timed = nullptr;      // the stream state of the latest timed add
 };
 
@@ -58,8 +59,19 @@ int add_plan(s3dg_chunks *h, const ChunkPlan &P, const void *base, uint64_t stri
     ChunkStream *Sp = nullptr;
     if (int r = h->stream_enter(s, &Sp)) return r;
     ChunkStream &S = *Sp;
+    // the parallel walk's part of the scratch, when an object of the add reaches the threshold
+    ChunkSearch Q{h->search_min, CsPlan{}, 0};
+    uint64_t nodes = 0;
+    if (Q.threshold && !C) nodes = P.n_objs * cs_reserved(P.len, Q.threshold, h->min_bytes, h->avg_bytes);
+    for (uint64_t k = 0; Q.threshold && C && k < n; ++k)
+        nodes += cs_reserved(spans[k].size, Q.threshold, h->min_bytes, h->avg_bytes);
+    const bool search = nodes > 0 && nodes <= kCsMaxNodes && P.granules <= kCsMaxGranules;
+    if (search) {
+        HIP_TRY(chunk_search_tmp_bytes(P.n_objs, P.granules, &Q.tmp_bytes), "hipcub scan size");
+        Q.plan = cs_plan(P.scratch_bytes, P.n_objs, P.granules, nodes, Q.tmp_bytes);
+    }
     // the stream's earlier add may still use the old scratch
-    if (int r = accum_regrow(&S.scratch, &S.cap, P.scratch_bytes, S.ev, "hipEventSynchronize(chunks add)",
+    if (int r = accum_regrow(&S.scratch, &S.cap, search ? Q.plan.end : P.scratch_bytes, S.ev, "hipEventSynchronize(chunks add)",
                              "hipMalloc(chunk scratch)"))
         return r;
     ChunkSrc src{(const uint8_t *)base, stride, nullptr, nullptr, 0, 0};
@@ -74,7 +86,8 @@ int add_plan(s3dg_chunks *h, const ChunkPlan &P, const void *base, uint64_t stri
             if (!S.tev[k]) HIP_TRY(hipEventCreate(&S.tev[k]), "hipEventCreate");
     const char *step = "";
     HIP_TRY(launch_chunk_passes(P, src, 32 - h->bits, h->table, h->min_bytes, h->max_bytes, S.scratch,
-                                h->fp + h->used, h->flen + h->used, h->tot, timing ? S.tev : nullptr, &step, s),
+                                h->fp + h->used, h->flen + h->used, h->tot, timing ? S.tev : nullptr, &step, s, search ? &Q : nullptr,
+                                h->avg_bytes),
             C ? "launch chunk batch passes" : step);
     if (timing) h->timed = &S;
     if (int r = h->stream_mark(S, s)) return r;
@@ -180,7 +193,18 @@ int s3dg_chunks_set_option(s3dg_chunks *h, int option, int value) {
     ACCUM_SCOPE(h, kNullHandle);
     if (option == S3DG_CHUNKS_TIME_PASSES) h->timing = value != 0;
     else if (option == S3DG_CHUNKS_GEAR_TABLE) h->table = value != 0;
+    else if (option == S3DG_CHUNKS_SEARCH_WALK) {
+        if (value < 0) return fail(S3DG_EINVAL, "the search walk's smallest object size must not be negative");
+        h->search_min = (uint64_t)value;
+    }
     else return fail(S3DG_EINVAL, "unknown chunks option");
+    return S3DG_OK;
+}
+
+int s3dg_chunks_search_geometry(uint32_t *hop_links, uint32_t *node_bytes) {
+    if (!hop_links || !node_bytes) return fail(S3DG_EINVAL, "null output");
+    *hop_links = kCsHop;
+    *node_bytes = kCsNodeBytes;
     return S3DG_OK;
 }
 

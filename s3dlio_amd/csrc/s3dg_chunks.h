@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "s3dg_chunk_plan.h"
+#include "s3dg_chunk_search_plan.h"
 #include "s3dg_measure.h"
 
 namespace s3dg {
@@ -27,7 +28,16 @@ struct ChunkSrc {
     uint32_t tshift;
 };
 
-// The three passes of one add, all through `scratch` (P.scratch_bytes).
+// An add whose objects of at least `threshold` bytes take the parallel cut walk
+// (S3DG_CHUNKS_SEARCH_WALK): its part of the scratch, behind
+// the plan's, and the bytes of hipCUB scratch in it.
+struct ChunkSearch {
+    uint64_t threshold;
+    CsPlan plan;
+    size_t tmp_bytes;
+};
+
+// The three passes of one add, all through `scratch` (P.scratch_bytes, or Q->plan.end).
 // A: the candidate bitmap (bit b of word 64 g + l of an object: its byte
 // 4096 g + 64 l + b is a candidate cut) and the candidates per granule, summed
 // into tot[kChunkTotCandidates]; shift = 32 - bits; table: the gear values from
@@ -35,11 +45,21 @@ struct ChunkSrc {
 // bitmap and writes the (offset, length) records of its chunks and their
 // count; chunks and forced cuts are added to tot.  C: one wave per record
 // slot: fp[i], flen[i] for slot i of the add (flen 0: the slot holds no chunk).
+// Q not null: pass B is launch_chunk_search for the objects it takes and the
+// wave per object for the rest, in the same add.
 // tev: null, or four events recorded around the passes.  *step names what was
 // being enqueued, for the label of a failure.
 hipError_t launch_chunk_passes(const ChunkPlan &P, const ChunkSrc &src, uint32_t shift, bool table,
                                uint64_t min_bytes, uint64_t max_bytes, void *scratch, MeasureFp *fp, uint32_t *flen,
-                               uint64_t *tot, hipEvent_t *tev, const char **step, hipStream_t s);
+                               uint64_t *tot, hipEvent_t *tev, const char **step, hipStream_t s, const ChunkSearch *Q = nullptr,
+                               uint64_t avg_bytes = 0);
+// The parallel form of pass B (s3dg_chunk_search.hip) over pass A's bitmap and
+// counts: the records, counts and totals of every object that CsObj.take marks
+// in the table it leaves at Q.plan.obj_off; the others are left to chunk_walk.
+hipError_t launch_chunk_search(const ChunkPlan &P, const ChunkSrc &src, const ChunkSearch &Q, uint64_t min_bytes,
+                               uint64_t avg_bytes, uint64_t max_bytes, void *scratch, uint64_t *tot, hipStream_t s);
+// hipCUB's scratch for the two sums of such an add.
+hipError_t chunk_search_tmp_bytes(uint64_t n_objs, uint64_t granules, size_t *bytes);
 // Distinct fingerprints among the n slots and the summed length of one chunk
 // each: two stable radix sorts of (key, slot index) in `work`
 // (chunk_sort_bytes(n) bytes, then *tmp_bytes of hipCUB scratch), added to

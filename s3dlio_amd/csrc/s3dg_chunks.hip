@@ -243,6 +243,31 @@ __global__ __launch_bounds__(256) void k_chunk_cuts_batch(const uint64_t *bitmap
     chunk_walk(bitmap + e.g0 * 64, j, e.size, minb, maxb, e.s0, roff, rlen, cnt, tot);
 }
 
+// With the parallel walk in the add (s3dg_chunk_search.hip): the same two
+// kernels for the objects it has left, by the table it built.  The batch form
+// names every entry's slots, whoever walks it.
+__global__ __launch_bounds__(256) void k_chunk_cuts_rest(const uint64_t *bitmap, uint64_t n_objs, uint64_t len,
+                                                         uint64_t wpo, uint64_t rpo, uint64_t minb, uint64_t maxb,
+                                                         uint64_t *roff, uint32_t *rlen, uint32_t *cnt, uint64_t *tot,
+                                                         const CsObj *obj) {
+    const uint64_t j = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= n_objs || obj[j].take) return;
+    chunk_walk(bitmap + j * wpo, j, len, minb, maxb, j * rpo, roff, rlen, cnt, tot);
+}
+
+__global__ __launch_bounds__(256) void k_chunk_cuts_batch_rest(const uint64_t *bitmap, const SpanEnt *ents,
+                                                               uint64_t live, uint64_t minb, uint64_t maxb,
+                                                               uint64_t *roff, uint32_t *rlen, uint32_t *cnt,
+                                                               uint32_t *own, uint64_t *tot, const CsObj *obj) {
+    const uint64_t j = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= live) return;
+    const SpanEnt e = ents[j];
+    const uint64_t slots = (e.size + minb - 1) / minb + 1;   // span_obj_slots
+    for (uint64_t k = threadIdx.x & 63; k < slots; k += 64) own[e.s0 + k] = (uint32_t)j;
+    if (obj[j].take) return;
+    chunk_walk(bitmap + e.g0 * 64, j, e.size, minb, maxb, e.s0, roff, rlen, cnt, tot);
+}
+
 // ---- pass C ---------------------------------------------------------------------
 // Bytes sh .. sh + 15 of the 32 bytes a | b, sh wave-uniform in [1, 15].
 __device__ __forceinline__ u32x4 shift_bytes(u32x4 a, u32x4 b, uint32_t sh) {
@@ -397,7 +422,8 @@ __global__ __launch_bounds__(256) void k_chunk_count(const MeasureFp *fp, const 
 
 hipError_t launch_chunk_passes(const ChunkPlan &P, const ChunkSrc &src, uint32_t shift, bool table,
                                uint64_t min_bytes, uint64_t max_bytes, void *scratch, MeasureFp *fp, uint32_t *flen,
-                               uint64_t *tot, hipEvent_t *tev, const char **step, hipStream_t s) {
+                               uint64_t *tot, hipEvent_t *tev, const char **step, hipStream_t s, const ChunkSearch *Q,
+                               uint64_t avg_bytes) {
     (void)hipGetLastError();
     uint8_t *sc = reinterpret_cast<uint8_t *>(scratch);
     uint64_t *bitmap = reinterpret_cast<uint64_t *>(sc);
@@ -446,7 +472,18 @@ hipError_t launch_chunk_passes(const ChunkPlan &P, const ChunkSrc &src, uint32_t
     *step = "launch k_chunk_cuts";
     const uint64_t gb = (P.n_objs + 3) / 4, gc = (P.slots + 3) / 4;
     if (gb > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (batch)
+    if (Q) {
+        *step = "launch chunk search";
+        if ((e = launch_chunk_search(P, src, *Q, min_bytes, avg_bytes, max_bytes, scratch, tot, s)) != hipSuccess)
+            return e;
+        const CsObj *obj = reinterpret_cast<const CsObj *>(sc + Q->plan.obj_off);
+        if (batch)
+            hipLaunchKernelGGL(k_chunk_cuts_batch_rest, dim3((uint32_t)gb), dim3(256), 0, s, bitmap, src.ents, P.n_objs,
+                               min_bytes, max_bytes, roff, rlen, cnt, own, tot, obj);
+        else
+            hipLaunchKernelGGL(k_chunk_cuts_rest, dim3((uint32_t)gb), dim3(256), 0, s, bitmap, P.n_objs, P.len, P.wpo,
+                               P.rpo, min_bytes, max_bytes, roff, rlen, cnt, tot, obj);
+    } else if (batch)
         hipLaunchKernelGGL(k_chunk_cuts_batch, dim3((uint32_t)gb), dim3(256), 0, s, bitmap, src.ents, P.n_objs,
                            min_bytes, max_bytes, roff, rlen, cnt, own, tot);
     else

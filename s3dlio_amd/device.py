@@ -322,6 +322,15 @@ def tfrecord_search_geometry() -> tuple[int, int]:
     return int(tile.value), int(hop.value)
 
 
+def chunks_search_geometry() -> tuple[int, int]:
+    """(hop_links, node_bytes) of the chunker's parallel cut walk
+    (Chunker.search_walk): the links one step of its remaining serial part
+    covers, a power of two, and the scratch bytes per node.  Needs no device."""
+    hop, node = _lib.c_u32(0), _lib.c_u32(0)
+    call("s3dg_chunks_search_geometry", ctypes.byref(hop), ctypes.byref(node))
+    return int(hop.value), int(node.value)
+
+
 def tfrecord_index_text(entries) -> str:
     """The DALI text form of an index, "{offset} {size}\\n" per record
     (index_text_from_bytes, src/tfrecord_index.rs:92-101): entries is an (n, 2)
@@ -357,7 +366,7 @@ def _tfr_var_shards(shards):
     return arr, len(rows), np.ascontiguousarray(cat, dtype=np.uint64), need_src, need_dst, need_idx
 
 
-_CHUNKS_TIME_PASSES, _CHUNKS_GEAR_TABLE = 1, 2   # S3DG_CHUNKS_* options
+_CHUNKS_TIME_PASSES, _CHUNKS_GEAR_TABLE, _CHUNKS_SEARCH_WALK = 1, 2, 4   # S3DG_CHUNKS_* options
 
 
 def _ptr(x) -> int:
@@ -876,30 +885,36 @@ class Context:
     # (avg_bytes: a power of two).  Every object is chunked on
     # its own from its first byte.
     def chunker(self, min_bytes: int = CHUNK_DEFAULTS[0], avg_bytes: int = CHUNK_DEFAULTS[1],
-                max_bytes: int = CHUNK_DEFAULTS[2]) -> "Chunker":
-        """An accumulating handle: add / add_stream on any stream, then result()."""
-        return Chunker(self, min_bytes, avg_bytes, max_bytes)
+                max_bytes: int = CHUNK_DEFAULTS[2], search_walk: int = 0) -> "Chunker":
+        """An accumulating handle: add / add_stream on any stream, then result().
+        search_walk: Chunker.search_walk's smallest object size (0: off)."""
+        h = Chunker(self, min_bytes, avg_bytes, max_bytes)
+        if search_walk:
+            h.search_walk(search_walk)
+        return h
 
     def measure_chunks(self, src, nbytes: int | None = None, min_bytes: int = CHUNK_DEFAULTS[0],
                        avg_bytes: int = CHUNK_DEFAULTS[1], max_bytes: int = CHUNK_DEFAULTS[2],
-                       stream=None) -> ChunkResult:
+                       stream=None, search_walk: int = 0) -> ChunkResult:
         """One object of `nbytes` at src."""
-        with self.chunker(min_bytes, avg_bytes, max_bytes) as h:
+        with self.chunker(min_bytes, avg_bytes, max_bytes, search_walk) as h:
             h.add(src, nbytes, stream=stream)
             return h.result()
 
     def measure_chunks_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None,
                               min_bytes: int = CHUNK_DEFAULTS[0], avg_bytes: int = CHUNK_DEFAULTS[1],
-                              max_bytes: int = CHUNK_DEFAULTS[2], stream=None) -> ChunkResult:
+                              max_bytes: int = CHUNK_DEFAULTS[2], stream=None,
+                              search_walk: int = 0) -> ChunkResult:
         """n_objs equal objects as fill_stream lays them out; stride gaps are never read."""
-        with self.chunker(min_bytes, avg_bytes, max_bytes) as h:
+        with self.chunker(min_bytes, avg_bytes, max_bytes, search_walk) as h:
             h.add_stream(src, obj_size, n_objs, stride, stream=stream)
             return h.result()
 
     def measure_chunks_batch(self, src, objects, min_bytes: int = CHUNK_DEFAULTS[0],
                              avg_bytes: int = CHUNK_DEFAULTS[1], max_bytes: int = CHUNK_DEFAULTS[2],
                              stream=None) -> ChunkResult:
-        """A mixed-size batch as fill_batch lays it out (Chunker.add_batch); gaps are never read."""
+        """A mixed-size batch as fill_batch lays it out (Chunker.add_batch); gaps are never read.
+        (For the parallel cut walk in a batch: chunker(..., search_walk=n) and add_batch.)"""
         with self.chunker(min_bytes, avg_bytes, max_bytes) as h:
             h.add_batch(src, objects, stream=stream)
             return h.result()
@@ -1244,6 +1259,14 @@ class Chunker(_Accum):
     def gear_table(self, on: bool = True) -> None:
         """The candidate pass's G from LDS (default) or computed per byte; same results."""
         call("s3dg_chunks_set_option", self._h, _CHUNKS_GEAR_TABLE, 1 if on else 0)
+
+    def search_walk(self, min_object_bytes: int) -> None:
+        """In the following adds, every object of at least this many bytes has
+        its cuts walked in parallel inside the object (DESIGN.md §5.11.1);
+        smaller ones keep one wave each.  0: off (default).  Same results
+        either way; it pays for large single objects and costs scratch
+        (chunks_search_geometry)."""
+        call("s3dg_chunks_set_option", self._h, _CHUNKS_SEARCH_WALK, int(min_object_bytes))
 
     def pass_seconds(self) -> tuple[float, float, float]:
         """Candidate, cut and fingerprint pass times of the latest timed add (waits for it)."""
