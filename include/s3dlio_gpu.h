@@ -695,6 +695,89 @@ int s3dg_lz_get(s3dg_lz *h, s3dg_lz_result *out);
  * len == 0: all zeros, no GPU needed. */
 int s3dg_lz_data(const uint8_t *buf, uint64_t len, uint64_t block_bytes, s3dg_lz_result *out);
 
+/* ---- dedup, then LZ4 on the blocks kept (read-only) ---------
+ * What a payload is worth to a store that deduplicates blocks of `block_bytes`
+ * and then compresses the blocks it keeps: the data reduction ratio, payload
+ * bytes over bytes kept after both steps, the answer to the generator's
+ * `dedup` and `compress` knobs together.  The product of the two handles'
+ * ratios above is that figure only when every distinct block compresses like
+ * the average block; ragged last blocks, zero blocks and a dedup unit larger
+ * than the store's block break it.  No seed is needed.
+ *
+ * block_bytes: a multiple of 4096 from 4096 to 65536.  Every object is cut
+ * into blocks from its first byte; the last block of an object has whatever
+ * length n >= 1 remains (s3dg_lz's rules and refusals).  Two blocks are the
+ * same when they have the same length and the same bytes.  Over everything
+ * added to the handle since it was created or reset, across adds and streams,
+ * every distinct block is counted once: unique_blocks and unique_bytes are
+ * their number and their summed length, and the six LZ fields are s3dg_lz's
+ * (steps 1-4 above) summed over the distinct blocks only.  Equal blocks parse
+ * equally, so it does not matter which occurrence is parsed.
+ * Blocks are compared through 128-bit fingerprints, s3dg_measure's: a ragged
+ * block never equals a full one (bytes and length are compared),
+ * unique_blocks is the exact number of distinct fingerprints, s3dg_measure's
+ * over the same adds, and two different blocks share one with probability
+ * about 2^-64 per pair for data that was not built against the (public,
+ * fixed) keys.
+ *
+ * A handle accumulates over adds on any stream, like s3dg_measure.  Every add
+ * makes two passes on its stream: the measure's fingerprint pass into the
+ * handle's kept array (16 bytes per block ever added, in an array that grows
+ * by doubling; 20 bytes per 4 KiB of the add as scratch per stream), then one
+ * wave per block that claims the block's fingerprint in the handle's table
+ * and loads and parses the block only if the claim is new: a duplicate block
+ * is never read a second time.  The table is open addressing in device
+ * memory, 8 bytes a slot (s3dg_reduce_geometry), a power of two of slots at
+ * least twice the blocks the handle holds, from 4096 slots on.  An add that
+ * would pass that bound first waits for the adds the handle has enqueued and
+ * rebuilds the table at its new size; so does growing the kept array.
+ * Out of scope: content-defined chunks as the dedup unit; any compressor but
+ * this one; emitting the compressed bytes; automatic choice of block_bytes; a
+ * bench.py config (tools/reduce_rate.py times the add).
+ * Destroy a handle before its context. */
+typedef struct s3dg_reduce s3dg_reduce;
+typedef struct {
+    uint64_t bytes;          /* payload bytes added (stride gaps excluded) */
+    uint64_t blocks;         /* blocks added, ragged last blocks included */
+    uint64_t unique_blocks;  /* distinct among them (bytes and length) */
+    uint64_t unique_bytes;   /* summed length of one block per distinct fingerprint */
+    uint64_t lz_bytes;       /* the rest over the distinct blocks: sum of size */
+    uint64_t stored_bytes;   /* sum of min(size, n): what the store keeps */
+    uint64_t raw_blocks;     /* blocks with size >= n */
+    uint64_t matches;
+    uint64_t match_bytes;    /* sum of L */
+    uint64_t literal_bytes;  /* literal_bytes + match_bytes == unique_bytes */
+} s3dg_reduce_result;
+int s3dg_reduce_create(s3dg_ctx *ctx, uint64_t block_bytes, s3dg_reduce **out);
+int s3dg_reduce_destroy(s3dg_reduce *h);
+/* Waits for the enqueued adds; an empty handle again: the totals and the table
+ * zeroed, the kept fingerprints forgotten (the arrays keep their size). */
+int s3dg_reduce_reset(s3dg_reduce *h);
+/* The arguments, ordering and refusals of s3dg_lz_add_stream, s3dg_lz_add_range
+ * and s3dg_lz_add_batch.  Slots of the kept array are reserved on the host
+ * under the handle's mutex, so adds from several threads on several streams
+ * are safe; two adds that run at once and hold the same block count it once.
+ * A refused add leaves the handle as it was.  An add that fails with S3DG_EHIP
+ * after its first launch may have left claims in the table: the handle then
+ * refuses adds and get (S3DG_EHIP, with a message that says so) until
+ * s3dg_reduce_reset. */
+int s3dg_reduce_add_stream(s3dg_reduce *h, const void *src, uint64_t obj_size, uint64_t stride,
+                           uint64_t n_objs, void *stream);
+int s3dg_reduce_add_range(s3dg_reduce *h, const void *src, uint64_t obj_size, uint64_t blk_lo,
+                          uint64_t blk_hi, void *stream);
+int s3dg_reduce_add_batch(s3dg_reduce *h, const void *src_base, const s3dg_span *spans, uint64_t n,
+                          void *stream);
+/* Waits for the enqueued adds and fills *out.  The handle is unchanged: get
+ * again, or add and get.  An empty handle yields all zeros. */
+int s3dg_reduce_get(s3dg_reduce *h, s3dg_reduce_result *out);
+/* The table's first size in slots and a slot's bytes.  Needs no device. */
+int s3dg_reduce_geometry(uint32_t *initial_slots, uint32_t *slot_bytes);
+/* A host buffer (any alignment, read-only memory included) as one object, on
+ * a host slot's GPU: copied in chunks of whole blocks (up to 64 MiB) on the
+ * slot's two streams in turn, each chunk an s3dg_reduce_add_range.
+ * len == 0: all zeros, no GPU needed. */
+int s3dg_reduce_data(const uint8_t *buf, uint64_t len, uint64_t block_bytes, s3dg_reduce_result *out);
+
 /* ---- memory / copy helpers ------------------------------------------------ */
 int s3dg_device_alloc(s3dg_ctx *ctx, uint64_t bytes, void **out);
 int s3dg_device_free(s3dg_ctx *ctx, void *p);

@@ -104,6 +104,13 @@ class LzRec(ctypes.Structure):
                 ("raw_blocks", c_u64), ("matches", c_u64), ("match_bytes", c_u64), ("literal_bytes", c_u64)]
 
 
+class ReduceRec(ctypes.Structure):
+    """s3dg_reduce_result"""
+    _fields_ = [("bytes", c_u64), ("blocks", c_u64), ("unique_blocks", c_u64), ("unique_bytes", c_u64),
+                ("lz_bytes", c_u64), ("stored_bytes", c_u64), ("raw_blocks", c_u64), ("matches", c_u64),
+                ("match_bytes", c_u64), ("literal_bytes", c_u64)]
+
+
 # name -> (restype, argtypes); the exact export list of include/s3dlio_gpu.h
 SIGNATURES = {
     "s3dg_ctx_create": (c_int, [c_int, ctypes.POINTER(c_vp)]),
@@ -184,6 +191,15 @@ SIGNATURES = {
     "s3dg_lz_add_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(Span), c_u64, c_vp]),
     "s3dg_lz_get": (c_int, [c_vp, ctypes.POINTER(LzRec)]),
     "s3dg_lz_data": (c_int, [c_vp, c_u64, c_u64, ctypes.POINTER(LzRec)]),
+    "s3dg_reduce_create": (c_int, [c_vp, c_u64, ctypes.POINTER(c_vp)]),
+    "s3dg_reduce_destroy": (c_int, [c_vp]),
+    "s3dg_reduce_reset": (c_int, [c_vp]),
+    "s3dg_reduce_add_stream": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp]),
+    "s3dg_reduce_add_range": (c_int, [c_vp, c_vp, c_u64, c_u64, c_u64, c_vp]),
+    "s3dg_reduce_add_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(Span), c_u64, c_vp]),
+    "s3dg_reduce_get": (c_int, [c_vp, ctypes.POINTER(ReduceRec)]),
+    "s3dg_reduce_geometry": (c_int, [ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
+    "s3dg_reduce_data": (c_int, [c_vp, c_u64, c_u64, ctypes.POINTER(ReduceRec)]),
     "s3dg_write_ceiling": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
     "s3dg_write_ceiling_tiled": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),
     "s3dg_write_ceiling_fill": (c_int, [c_vp, c_vp, c_u64, c_u32, c_vp]),

@@ -1,9 +1,10 @@
 // s3dg_accum.h — the core of an accumulating handle: what s3dg_measure,
-// s3dg_chunks and s3dg_lz share behind their C ABI.
+// s3dg_chunks, s3dg_lz and s3dg_reduce share
+// behind their C ABI.
 // A handle takes adds on any stream, sums into device totals that only take
 // atomics, and reads them back on a stream of its own.  Also the driver of the
-// host-buffer forms (s3dg_measure_data, s3dg_chunk_data, s3dg_lz_data) over a
-// host slot's staging set.  Private to those three units.
+// host-buffer forms (s3dg_measure_data, s3dg_chunk_data, s3dg_lz_data,
+// s3dg_reduce_data) over a host slot's staging set.  Private to those four units.
 #pragma once
 #include "s3dg_ctx.h"
 #include "s3dg_span_batch_plan.h"

@@ -200,6 +200,41 @@ class LzResult:
                    int(r.matches), int(r.match_bytes), int(r.literal_bytes))
 
 
+@dataclass(frozen=True)
+class ReduceResult:
+    """s3dg_reduce_result: what a payload takes in a store that deduplicates
+    blocks and compresses the ones it keeps with a greedy LZ4."""
+    bytes: int = 0            # payload bytes added (stride gaps excluded)
+    blocks: int = 0           # blocks added, ragged last blocks included
+    unique_blocks: int = 0    # distinct among them (bytes and length)
+    unique_bytes: int = 0     # summed length of one block per distinct fingerprint
+    lz_bytes: int = 0         # the rest over the distinct blocks: summed LZ4 block sizes
+    stored_bytes: int = 0     # summed min(size, n): what the store keeps
+    raw_blocks: int = 0       # blocks with size >= n
+    matches: int = 0
+    match_bytes: int = 0
+    literal_bytes: int = 0    # literal_bytes + match_bytes == unique_bytes
+
+    @property
+    def dedup_ratio(self) -> float:
+        """blocks / unique_blocks: what deduplication alone saves (n : 1)."""
+        return self.blocks / self.unique_blocks if self.unique_blocks else 0.0
+
+    @property
+    def compress_ratio(self) -> float:
+        """unique_bytes / stored_bytes: what compression saves on the blocks kept."""
+        return self.unique_bytes / self.stored_bytes if self.stored_bytes else 0.0
+
+    @property
+    def reduction_ratio(self) -> float:
+        """bytes / stored_bytes: the store's data reduction ratio, both steps."""
+        return self.bytes / self.stored_bytes if self.stored_bytes else 0.0
+
+    @classmethod
+    def _of(cls, r) -> "ReduceResult":
+        return cls(*(int(getattr(r, f[0])) for f in _lib.ReduceRec._fields_))
+
+
 CHUNK_DEFAULTS = (2048, 8192, 65536)   # min_bytes, avg_bytes, max_bytes
 @dataclass(frozen=True)
 class TfRecordResult:
@@ -947,6 +982,36 @@ class Context:
             m.add_batch(src, objects, stream=stream)
             return m.result()
 
+    # -- dedup, then LZ4 on the blocks kept (read-only) -----------------------------
+    # The bytes a payload takes in a store that deduplicates blocks of
+    # `block_bytes` (a multiple of 4096 up to 65536) and compresses the
+    # distinct ones with a greedy LZ4: its data reduction ratio (DESIGN.md
+    # §5.14).  Blocks are cut from each object's start.
+    def reducer(self, block_bytes: int = 65536) -> "Reducer":
+        """An accumulating handle: add / add_stream / add_range / add_batch on
+        any stream, then result()."""
+        return Reducer(self, block_bytes)
+
+    def measure_reduction(self, src, nbytes: int | None = None, block_bytes: int = 65536,
+                          stream=None) -> ReduceResult:
+        """One object of `nbytes` at src."""
+        with self.reducer(block_bytes) as m:
+            m.add(src, nbytes, stream=stream)
+            return m.result()
+
+    def measure_reduction_stream(self, src, obj_size: int, n_objs: int, stride: int | None = None,
+                                 block_bytes: int = 65536, stream=None) -> ReduceResult:
+        """n_objs equal objects as fill_stream lays them out; stride gaps are never read."""
+        with self.reducer(block_bytes) as m:
+            m.add_stream(src, obj_size, n_objs, stride, stream=stream)
+            return m.result()
+
+    def measure_reduction_batch(self, src, objects, block_bytes: int = 65536, stream=None) -> ReduceResult:
+        """A mixed-size batch as fill_batch lays it out (Reducer.add_batch); gaps are never read."""
+        with self.reducer(block_bytes) as m:
+            m.add_batch(src, objects, stream=stream)
+            return m.result()
+
     # -- checksums of a mixed-size batch (read-only) --------------------------------
     def crc32_batch(self, src, objects, stream=None, out=None):
         """The CRC-32 (zlib.crc32) of every object of a mixed-size batch in one
@@ -1139,7 +1204,7 @@ class Context:
 
 
 class _Accum:
-    """What Measure, LzMeasure and Chunker share: a C handle s3dg_<_sym>_* that
+    """What Measure, LzMeasure, Reducer and Chunker share: a C handle s3dg_<_sym>_* that
     accumulates over calls and streams.  A subclass names the symbol prefix
     (_sym), the result record of _lib (_rec), turns one into its result
     (_result) and creates the handle with _open(*create_args)."""
@@ -1238,6 +1303,27 @@ class LzMeasure(_BlockAccum):
     def __init__(self, ctx: Context, block_bytes: int = 65536):
         self.block_bytes = int(block_bytes)
         self._open(ctx, self.block_bytes)
+
+
+class Reducer(_BlockAccum):
+    """s3dg_reduce: a dedup-then-compress measurement that accumulates over
+    calls and streams (Context.reducer): every distinct block is counted and
+    parsed once, whichever add brought it.  The adds are asynchronous on their
+    stream and ordered like a fill, so a following launch on the same stream
+    may overwrite the buffer; result() waits for them and leaves the handle
+    unchanged."""
+    _sym, _rec, _result = "reduce", _lib.ReduceRec, staticmethod(ReduceResult._of)
+
+    def __init__(self, ctx: Context, block_bytes: int = 65536):
+        self.block_bytes = int(block_bytes)
+        self._open(ctx, self.block_bytes)
+
+
+def reduce_geometry() -> tuple[int, int]:
+    """(initial_slots, slot_bytes) of a Reducer's claim table; needs no device."""
+    a, b = c_u32(), c_u32()
+    call("s3dg_reduce_geometry", ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
 
 
 class Chunker(_Accum):
