@@ -1019,6 +1019,69 @@ int s3dg_tfrecord_index_search_timed(s3dg_ctx *ctx, const void *base, void *idx_
 /* The search's two constants, for placing test edges: positions per tile and
  * records per hop, both powers of two.  No context, no device. */
 int s3dg_tfrecord_search_geometry(uint32_t *tile_bytes, uint32_t *hop_records);
+/* The payloads of indexed records copied out of framed streams, every copied
+ * record checked in the same pass.  The only description is
+ * what s3dg_tfrecord_index_batch left in device memory.  A take is a run of
+ * consecutive records of one index; a run of count == 1 is a pick, and a
+ * shuffled batch of B rows is B takes with dst_off = k * row_stride,
+ * dst_cap = row_stride.  Takes may come in any order, repeat, share a stream
+ * and have count == 0 (nothing read or written, status 0). */
+typedef struct {
+    uint64_t off;       /* the framed stream starts at base + off, any byte offset (as s3dg_tfrecord_stream.off) */
+    uint64_t bytes;     /* its length; no byte outside [off, off + bytes) is read */
+    uint64_t idx_off;   /* its index entries, as s3dg_tfrecord_index_batch writes them, at idx_base + idx_off (multiple of 16) */
+    uint64_t first;     /* take records [first, first + count) of that index */
+    uint64_t count;
+    uint64_t dst_off;   /* their payloads, packed back to back, at dst_base + dst_off (multiple of 16) */
+    uint64_t dst_cap;   /* bytes that may be written there */
+} s3dg_tfrecord_take;
+typedef struct {
+    uint64_t records, bytes;          /* records taken, payload bytes written */
+    uint64_t status;                  /* 0 taken; 1 payload exceeds dst_cap; 2 the entries do not describe the stream */
+    uint64_t bad_records, bad_length, bad_length_crc, bad_data_crc;   /* as s3dg_tfrecord_result */
+    uint64_t first_take, first_record;   /* first take (caller's index) with a bad record, and its lowest bad record; UINT64_MAX when clean */
+} s3dg_tfrecord_extract_result;
+/* Synchronous on `stream`; `takes` is consumed before it returns; per_take
+ * (a host array of n) may be NULL.  With e_i = <o_i, s_i> the i-th entry of a
+ * take's index, record i's payload is the s_i - 16 bytes at off + o_i + 12 and
+ * lands at dst_off + (o_i - o_first) - 16 (i - first).
+ * The entries are validated on the device before anything of the take is
+ * copied: every s_i >= 16, o_i + s_i == o_{i+1} inside the run, o_i + s_i <=
+ * bytes, no 64-bit wrap.  A take that fails is status 2: it reads no stream
+ * byte and writes nothing.  Reading 16 * (first + count) bytes of index memory
+ * at idx_off is the caller's contract; what they say is not.  A take whose
+ * payload exceeds dst_cap is status 1 and writes nothing; other takes are
+ * unaffected.  A taken take writes exactly [dst_off, dst_off + payload), every
+ * byte once; destination spans must not overlap each other or any stream.
+ * Reads are aligned dwords, each holding a byte of the record it serves.
+ * Per record the three classes of s3dg_tfrecord_result: the length field
+ * against s_i - 16, the length CRC against that length's, the footer against
+ * the data's masked CRC.  The copy goes by the index and delivers the bytes as
+ * they stand: a bad record is reported, not withheld.  first_record is the
+ * record's number in its index (first + i).  A clean call costs no atomic
+ * beyond one per record longer than a region.  total sums the takes; its
+ * status is the maximum over them; records and bytes count taken takes.
+ * Scratch: 64 bytes per take and 28 bytes per record, kept with the stream's
+ * state.  Refusals (S3DG_EINVAL, before anything is reserved or enqueued):
+ * "null context", "null base", "null idx_base", "null dst_base", "null
+ * output", "null take array", a misaligned idx_base or dst_base, more than
+ * 2^32 - 1 takes, and per take ("take k: ...") idx_off or dst_off no multiple
+ * of 16, first + count, off + bytes, dst_off + dst_cap or the index's end
+ * overflowing, more than 2^31 - 2 records in one call, more than 2^46 stream
+ * bytes in one call (a take counts min(bytes, dst_cap + 16 count), what it can
+ * read).  n == 0 succeeds whatever the other pointers.
+ * Holding a TFRecord object read back from a store to its seed (extract, then
+ * s3dg_verify_* on the result) is the follow-up and not part of this call. */
+int s3dg_tfrecord_extract_batch(s3dg_ctx *ctx, const void *base, const void *idx_base, void *dst_base,
+                                const s3dg_tfrecord_take *takes, uint64_t n, void *stream,
+                                s3dg_tfrecord_extract_result *total, s3dg_tfrecord_extract_result *per_take);
+/* The same call with its passes timed by device events: pass_ms[3] gets the
+ * milliseconds of the plan (validation and constants), the scan, and the copy
+ * with its fold ("null pass_ms"). */
+int s3dg_tfrecord_extract_timed(s3dg_ctx *ctx, const void *base, const void *idx_base, void *dst_base,
+                                const s3dg_tfrecord_take *takes, uint64_t n, void *stream,
+                                s3dg_tfrecord_extract_result *total, s3dg_tfrecord_extract_result *per_take,
+                                float *pass_ms);
 /* zlib crc32_combine: CRC of A||B from crc(A), crc(B), |B| (host). */
 uint32_t s3dg_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2);
 /* Host CRC-32 update (crc32fast::Hasher semantics: start from 0). */

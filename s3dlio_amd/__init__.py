@@ -8,7 +8,8 @@ the library is absent (no CPU fallback exists).
 from ._lib import S3dgError, lib  # noqa: F401  (loads libs3dlio_amd.so)
 from .hostbuf import BytesView  # noqa: F401
 from .device import (BLOCK_SIZE, DEFAULT_BASE_SEED, BatchVerifyResult, ChunkResult, Chunker, Context, LzMeasure,  # noqa: F401
-                     LzResult, Measure, MeasureResult, ReduceResult, Reducer, TfRecordResult, TfRecordWalk, VerifyResult,
+                     LzResult, Measure, MeasureResult, ReduceResult, Reducer, TfRecordExtract, TfRecordResult, TfRecordWalk,
+                     VerifyResult,
                      chunks_search_geometry, compress_ratio,
                      device_count, host_context, host_slots, object_entropy, parse_devices, reduce_geometry,
                      tfrecord_index_text,

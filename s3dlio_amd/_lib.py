@@ -86,6 +86,18 @@ class TfrWalkRec(ctypes.Structure):
                 ("bad_length_crc", c_u64), ("first_bad_record", c_u64)]
 
 
+class TfrTake(ctypes.Structure):
+    """s3dg_tfrecord_take"""
+    _fields_ = [("off", c_u64), ("bytes", c_u64), ("idx_off", c_u64), ("first", c_u64), ("count", c_u64),
+                ("dst_off", c_u64), ("dst_cap", c_u64)]
+
+
+class TfrExtractRec(ctypes.Structure):
+    """s3dg_tfrecord_extract_result"""
+    _fields_ = [("records", c_u64), ("bytes", c_u64), ("status", c_u64), ("bad_records", c_u64), ("bad_length", c_u64),
+                ("bad_length_crc", c_u64), ("bad_data_crc", c_u64), ("first_take", c_u64), ("first_record", c_u64)]
+
+
 class MeasureRec(ctypes.Structure):
     """s3dg_measure_result"""
     _fields_ = [("bytes", c_u64), ("zero_bytes", c_u64), ("blocks", c_u64), ("unique_blocks", c_u64),
@@ -249,6 +261,11 @@ SIGNATURES = {
     "s3dg_tfrecord_index_search_timed": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(TfrStream), c_u64, c_vp,
                                                  ctypes.POINTER(TfrWalkRec), ctypes.POINTER(ctypes.c_float)]),
     "s3dg_tfrecord_search_geometry": (c_int, [ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
+    "s3dg_tfrecord_extract_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(TfrTake), c_u64, c_vp,
+                                            ctypes.POINTER(TfrExtractRec), ctypes.POINTER(TfrExtractRec)]),
+    "s3dg_tfrecord_extract_timed": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(TfrTake), c_u64, c_vp,
+                                            ctypes.POINTER(TfrExtractRec), ctypes.POINTER(TfrExtractRec),
+                                            ctypes.POINTER(ctypes.c_float)]),
     "s3dg_crc32_combine": (c_u32, [c_u32, c_u32, c_u64]),
     "s3dg_crc32_host": (c_u32, [c_u32, c_vp, c_u64]),
     "s3dg_npz_size": (c_int, [ctypes.POINTER(c_u64), c_int, ctypes.c_char_p, c_u64,

@@ -15,6 +15,7 @@
 #include "s3dg_tfrecord_plan.h"     // TfrCounts, the TFRecord calls' table
 #include "s3dg_tfrecord_var_plan.h" // TfvCounts, the per-record table
 #include "s3dg_tfrecord_search_plan.h" // TfsPlanA, TfsPlanB: the search's workspaces
+#include "s3dg_tfrecord_extract_plan.h" // TfxCounts, TfxLayout: the extract's workspace
 #include "s3dg_prefix.h"            // PrefixParams and the one function that makes them
 
 // Sets the calling thread's error text (s3dg_last_error) and returns code.
@@ -414,6 +415,17 @@ hipError_t tfrecord_search_candidates(const uint8_t *base, const uint8_t *wa, co
 hipError_t tfrecord_search_resolve(const uint8_t *base, uint8_t *idx, const uint8_t *wa, const TfsPlanA &A, uint8_t *wb,
                                    const TfsPlanB &B, uint64_t n, uint64_t tiles, uint32_t nodes, int cus, hipEvent_t *marks,
                                    hipStream_t s);
+// Payloads out of framed streams by their index (s3dg_tfrecord_extract.hip;
+// s3dg_tfrecord_extract_plan.h).  ws is the workspace of tfx_layout with the
+// powers and the takes uploaded and the results reset.  Validation and the
+// records' constants, the scan over their region counts
+// (tfrecord_search_scan), the copy-and-hash launch over the host's bound of
+// regions and, when the call can have long records, a thread per such record.
+// The events (nullable, 4) are recorded at the start and behind the plan, the
+// scan, and the copy with its fold.
+hipError_t tfrecord_extract_launch(const uint8_t *src, const uint8_t *idx, uint8_t *dst, uint8_t *ws, const TfxLayout &L,
+                                   const TfxCounts &C, uint64_t n, size_t scan_tmp_bytes, void *tab_dev, int cus,
+                                   hipEvent_t *marks, hipStream_t s);
 
 // ---- NUMA placement of host buffers (s3dg_numa.cpp) -------------------------
 bool device_local_cpus(int device, cpu_set_t *out);

@@ -311,11 +311,48 @@ class TfRecordWalk:
     def ok(self) -> bool:
         return self.status == "complete" and self.bad_length_crc == 0
 
+    @property
+    def payload_bytes(self) -> int:
+        """Payload bytes of the records found: what one take of all of them
+        (Context.tfrecord_extract_batch) writes."""
+        return self.stop_offset - 16 * self.records
+
     @classmethod
     def _of(cls, r) -> "TfRecordWalk":
         fb = int(r.first_bad_record)
         return cls(int(r.records), _WALK_STATUS[int(r.status)], int(r.stop_offset), int(r.trailing),
                    int(r.bad_length_crc), None if fb == 2**64 - 1 else fb)
+
+
+_EXTRACT_STATUS = ("taken", "capacity", "index")
+
+
+@dataclass(frozen=True)
+class TfRecordExtract:
+    """What Context.tfrecord_extract_batch did (s3dg_tfrecord_extract_result):
+    the totals over the takes and, unless it was called with per_take=False,
+    one TfRecordExtract per take."""
+    records: int = 0              # records of the takes that were taken
+    bytes: int = 0                # payload bytes written
+    status: str = "taken"         # "taken" | "capacity" (payload exceeds dst_cap) | "index" (entries do not describe the stream)
+    bad_records: int = 0          # copied records bad in at least one of the three classes below
+    bad_length: int = 0           # length field differs from the entry's size - 16
+    bad_length_crc: int = 0       # length CRC differs from that length's
+    bad_data_crc: int = 0         # footer differs from the data's masked CRC
+    first_take: int | None = None     # index of the first take with a bad record; None = clean
+    first_record: int | None = None   # its lowest bad record, numbered as in its index
+    takes: tuple | None = None    # per take, in the caller's order; None in a take's own record and with per_take=False
+
+    @property
+    def ok(self) -> bool:
+        return self.status == "taken" and self.bad_records == 0
+
+    @classmethod
+    def _of(cls, r, takes=None) -> "TfRecordExtract":
+        none = 2**64 - 1
+        ft, fr = int(r.first_take), int(r.first_record)
+        return cls(int(r.records), int(r.bytes), _EXTRACT_STATUS[int(r.status)], int(r.bad_records), int(r.bad_length),
+                   int(r.bad_length_crc), int(r.bad_data_crc), None if ft == none else ft, None if fr == none else fr, takes)
 
 
 def _tfr_lengths(lengths) -> np.ndarray:
@@ -1131,6 +1168,45 @@ class Context:
         faster (DESIGN.md §5.5.3 has the figures).  Scratch of about a fifth
         of the streams' bytes is kept with the stream's state."""
         return self._tfrecord_walks("s3dg_tfrecord_index_search_batch", src, streams, index, stream)
+
+    def tfrecord_extract_batch(self, src, index, dst, takes, stream=None, per_take: bool = True) -> TfRecordExtract:
+        """The payloads of indexed records out of framed streams in one device
+        call, every copied record checked as tfrecord_check_var_batch checks
+        it.  Each take is (off, bytes, idx_off, first, count, dst_off,
+        dst_cap): of the stream of `bytes` at src + off (any byte offset)
+        whose entries tfrecord_index_batch left at index + idx_off, records
+        [first, first + count) go packed back to back to dst + dst_off, at
+        most dst_cap bytes.  One take built from a TfRecordWalk (count =
+        records, dst_cap = payload_bytes) unframes a whole stream; B takes of
+        count 1 with dst_off = k * row_stride gather a shuffled batch into
+        rows.  idx_off and dst_off are multiples of 16; takes may come in any
+        order, repeat, share a stream and be empty.  The entries are
+        validated on the device before anything of the take is copied: a take
+        whose entries do not describe its stream ("index") or whose payload
+        exceeds dst_cap ("capacity") writes nothing, the others are
+        unaffected.  A bad record is delivered as it stands and reported.
+        Spans are checked against the tensors' sizes before any launch
+        (ValueError).  Synchronous on `stream`; per_take=False asks for the
+        totals only."""
+        rows = [tuple(int(x) for x in tk) for tk in takes]
+        if any(len(tk) != 7 for tk in rows):
+            raise ValueError("a take is (off, bytes, idx_off, first, count, dst_off, dst_cap)")
+        if any(x < 0 or x >= 2**64 for tk in rows for x in tk):
+            raise ValueError("take fields must fit 64 unsigned bits")
+        n = len(rows)
+        arr = (_lib.TfrTake * max(1, n))()
+        need_src = need_idx = need_dst = 0
+        for k, tk in enumerate(rows):
+            arr[k] = _lib.TfrTake(*tk)
+            off, nbytes, idx_off, first, count, dst_off, dst_cap = tk
+            need_src = max(need_src, off + nbytes)
+            need_idx = max(need_idx, idx_off + 16 * (first + count))
+            need_dst = max(need_dst, dst_off + dst_cap)
+        tot = _lib.TfrExtractRec(0, 0, 0, 0, 0, 0, 0, 2**64 - 1, 2**64 - 1)
+        per = (_lib.TfrExtractRec * max(1, n))() if per_take else None
+        call("s3dg_tfrecord_extract_batch", self._h, self._src(src, need_src), self._src(index, need_idx),
+             self._dst(dst, need_dst), arr, n, self._s(stream), ctypes.byref(tot), per)
+        return TfRecordExtract._of(tot, tuple(TfRecordExtract._of(per[k]) for k in range(n)) if per_take else None)
 
     def _tfrecord_walks(self, sym, src, streams, index, stream) -> list:
         rows = [tuple(int(x) for x in st) for st in streams]
