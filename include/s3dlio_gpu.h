@@ -1093,6 +1093,93 @@ int s3dg_npz_size(const uint64_t *shape, int ndim, const char *dtype, uint64_t n
  * byte-identical archive (x.npy keystream + CRC on the GPU, framing on host). */
 int s3dg_npz_build(s3dg_ctx *ctx, const uint64_t *shape, int ndim, const char *dtype,
                    uint64_t num_samples, uint8_t *out, uint64_t out_len);
+/* ---- NPZ archives framed and checked on the device ----
+ * A list of stored ZIP archives, each of any number of member arrays, written
+ * into device memory in one call and checked there by its twin.  Per member
+ * the archive holds a local header, the name, the NPY header and the payload;
+ * one central entry per member and the end record follow the last member.
+ * The header fields are write_local_file_header, write_central_dir_entry and
+ * write_eocd (src/data_formats/npz.rs:254-309) for S3DG_NPZ_STYLE_RAW and
+ * s3dg_build_npz's for S3DG_NPZ_STYLE_LEGACY; a member's CRC-32 is that of its
+ * NPY header followed by its payload.  Members "x.npy" (the keystream) and
+ * "y.npy" (S3DG_NPZ_ZEROS) in STYLE_RAW give generate_npz_bytes_raw's bytes;
+ * one member "data.npy" with the '|u1' header in STYLE_LEGACY gives
+ * s3dg_build_npz's.  Names and NPY headers are host bytes in `blob`; only they
+ * and the descriptors cross the bus.
+ * There is no ZIP64.  The reference truncates sizes and offsets with `as u32`
+ * and then writes an archive nobody can read; these calls refuse instead: a
+ * member whose hdr_len + size reaches 2^32, and an archive in which a local
+ * header's offset, the central directory's offset or its size reaches 2^32. */
+#define S3DG_NPZ_ZEROS UINT64_MAX        /* src_off of a member whose payload is `size` zero bytes: no source is read */
+enum { S3DG_NPZ_STYLE_RAW = 0,           /* header fields of generate_npz_bytes_raw (npz.rs:254-309): version 20/20, time and date 0 */
+       S3DG_NPZ_STYLE_LEGACY = 1 };      /* header fields of s3dg_build_npz / object_frame: version needed 10, date 0x21 */
+typedef struct {
+    uint64_t src_off;                    /* payload at src_base + src_off (multiple of 16), or S3DG_NPZ_ZEROS */
+    uint64_t size;                       /* payload bytes; 0 is a valid member */
+    uint32_t name_off, name_len;         /* the member's file name in `blob` (1..65535 bytes, ".npy" included by the caller) */
+    uint32_t hdr_off, hdr_len;           /* the member's NPY header bytes in `blob` (may be 0: a raw stored file) */
+} s3dg_npz_member;
+typedef struct {
+    uint64_t dst_off;                    /* the archive at dst_base + dst_off, a multiple of 16 */
+    uint64_t member0, members;           /* members[member0 .. member0 + members), 1..65535 */
+    uint32_t style, pad;
+} s3dg_npz_archive;
+typedef struct {
+    uint64_t members, bad_members;       /* members looked at / with at least one of the next two */
+    uint64_t bad_local;                  /* local header, name or NPY header bytes differ from what the descriptor gives */
+    uint64_t bad_crc;                    /* CRC-32 of NPY header || payload as they lie in memory differs from the local header's field */
+    uint64_t bad_directory;              /* archives whose central directory or end record differ (CRC fields against the recomputed CRC) */
+    uint64_t first_archive, first_member;/* caller's index of the first bad archive, its lowest bad member (UINT64_MAX when clean, or when only the directory is bad) */
+} s3dg_npz_result;
+/* Bytes of an archive of these members: sum(30 + name_len + hdr_len + size +
+ * 46 + name_len) + 22.  No context, no blob.  S3DG_EINVAL when the sum
+ * overflows, when out is null, or when m is null with members present. */
+int s3dg_npz_archive_size(const s3dg_npz_member *m, uint64_t members, uint64_t *out);
+/* Frames every archive of the list in one call; s3dg_tfrecord_frame_batch's
+ * contract.  Ordered on `stream`, returns without a wait; `archives`,
+ * `members` and `blob` (host arrays) are consumed before it returns.  Archives
+ * may come in any order and may share members and sources.  src_base and
+ * dst_base are 16-byte aligned device pointers.
+ * Writes exactly the bytes of each archive: no byte before dst_off, none at or
+ * past the archive's ragged end (a neighbour may start at the next multiple of
+ * 16), and every byte once.  A payload lands at any residue mod 16, which
+ * differs from member to member: stores are aligned 16-byte pieces, the ragged
+ * first and last piece of a payload go byte by byte.  Source reads are aligned
+ * dwords, each holding a byte of the member's [src_off, src_off + size); a
+ * S3DG_NPZ_ZEROS member reads nothing.  Archives must not overlap each other
+ * or any source (the caller's contract); overlap of an archive and one of its
+ * own sources is refused.
+ * Refusals (S3DG_EINVAL, each with a message; every descriptor is checked
+ * before anything is reserved or enqueued, so a refused call has read and
+ * written nothing): "null context", a null or misaligned base, null arrays,
+ * per archive ("archive k: ...") dst_off no multiple of 16, an unknown style,
+ * no members or more than 65535, member0 + members beyond nmembers, the
+ * central directory's offset or size reaching 2^32, an end address
+ * overflowing, more than 2^46 archive bytes in one call; per member
+ * ("member j: ...", j its place in `members`) src_off no multiple of 16,
+ * name_len outside 1..65535, a name or header range outside `blob`,
+ * hdr_len + size reaching 2^32, its local header's offset reaching 2^32.
+ * n == 0 succeeds whatever the other pointers. */
+int s3dg_npz_frame_batch(s3dg_ctx *ctx, const void *src_base, void *dst_base, const s3dg_npz_archive *archives, uint64_t n,
+                         const s3dg_npz_member *members, uint64_t nmembers, const uint8_t *blob, uint64_t blob_len,
+                         void *stream);
+/* The read-side twin over the same descriptors (src_off is not looked at): the
+ * archive is at base + dst_off.  Synchronous on `stream`; writes nothing to
+ * the archives, and a clean archive costs no atomic.  Per member: the local
+ * header, the name and the NPY header against what the descriptors give
+ * (bad_local; a descriptor whose size is not the archive's shows here), and
+ * the local header's CRC field against the CRC-32 of the NPY header and the
+ * payload in memory (bad_crc; where the NPY header itself differs that is
+ * bad_local alone).  Per archive: the central directory and the end record
+ * (bad_directory); a central entry's CRC field is wrong when it is neither the
+ * recomputed CRC nor the local header's field, so damage to a payload or to a
+ * local CRC field is reported once, as bad_crc.  total (required) sums the
+ * archives; per_archive (host array of n, or NULL) gets every archive's own
+ * result, first_archive being k or UINT64_MAX.  Refusals as above, and "null
+ * output". */
+int s3dg_npz_check_batch(s3dg_ctx *ctx, const void *base, const s3dg_npz_archive *archives, uint64_t n,
+                         const s3dg_npz_member *members, uint64_t nmembers, const uint8_t *blob, uint64_t blob_len,
+                         void *stream, s3dg_npz_result *total, s3dg_npz_result *per_archive);
 
 /* ---- streaming generator (DataGenerator / ObjectGen / PyO3 Generator) ----- */
 /* One object of `size` bytes in the DG1 layout, generated on a host slot's

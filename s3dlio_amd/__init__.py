@@ -8,10 +8,12 @@ the library is absent (no CPU fallback exists).
 from ._lib import S3dgError, lib  # noqa: F401  (loads libs3dlio_amd.so)
 from .hostbuf import BytesView  # noqa: F401
 from .device import (BLOCK_SIZE, DEFAULT_BASE_SEED, BatchVerifyResult, ChunkResult, Chunker, Context, LzMeasure,  # noqa: F401
-                     LzResult, Measure, MeasureResult, ReduceResult, Reducer, TfRecordExtract, TfRecordResult, TfRecordWalk,
+                     LzResult, Measure, MeasureResult, NPZ_STYLE_LEGACY, NPZ_STYLE_RAW, NpzResult, ReduceResult, Reducer,
+                     TfRecordExtract, TfRecordResult, TfRecordWalk,
                      VerifyResult,
                      chunks_search_geometry, compress_ratio,
-                     device_count, host_context, host_slots, object_entropy, parse_devices, reduce_geometry,
+                     device_count, host_context, host_slots, npz_archive_size, object_entropy, parse_devices,
+                     reduce_geometry,
                      tfrecord_index_text,
                      tfrecord_search_geometry, tfrecord_size, tfrecord_var_size, unique_blocks, xoshiro_jump)
 from .data_gen import (HostRegistration, fill_controlled_data, fill_controlled_data_seeded,  # noqa: F401
@@ -24,7 +26,7 @@ from .datagen import (DataGenerator, Generator, ObjectGen, default_data_gen_thre
                       total_cpus, NumaMode, GeneratorConfig, DataBuffer, ObjectGenAlt,
                       generate_data_from_config, generate_data_simple, generate_data_with_config)
 
-from .npz import crc32_combine, crc32_device, generate_npz_bytes, npz_size  # noqa: F401
+from .npz import crc32_combine, crc32_device, generate_npz_bytes, npy_header, npy_header_u1, npz_size  # noqa: F401
 
 from .objects import (Config, DataGenMode, ObjectType, build_npz, build_raw,  # noqa: F401
                       build_tfrecord, build_tfrecord_with_index, generate_object,

@@ -98,6 +98,23 @@ class TfrExtractRec(ctypes.Structure):
                 ("bad_length_crc", c_u64), ("bad_data_crc", c_u64), ("first_take", c_u64), ("first_record", c_u64)]
 
 
+class NpzMember(ctypes.Structure):
+    """s3dg_npz_member"""
+    _fields_ = [("src_off", c_u64), ("size", c_u64), ("name_off", c_u32), ("name_len", c_u32), ("hdr_off", c_u32),
+                ("hdr_len", c_u32)]
+
+
+class NpzArchive(ctypes.Structure):
+    """s3dg_npz_archive"""
+    _fields_ = [("dst_off", c_u64), ("member0", c_u64), ("members", c_u64), ("style", c_u32), ("pad", c_u32)]
+
+
+class NpzRec(ctypes.Structure):
+    """s3dg_npz_result"""
+    _fields_ = [("members", c_u64), ("bad_members", c_u64), ("bad_local", c_u64), ("bad_crc", c_u64),
+                ("bad_directory", c_u64), ("first_archive", c_u64), ("first_member", c_u64)]
+
+
 class MeasureRec(ctypes.Structure):
     """s3dg_measure_result"""
     _fields_ = [("bytes", c_u64), ("zero_bytes", c_u64), ("blocks", c_u64), ("unique_blocks", c_u64),
@@ -272,6 +289,11 @@ SIGNATURES = {
                               ctypes.POINTER(c_u64)]),
     "s3dg_npz_build": (c_int, [c_vp, ctypes.POINTER(c_u64), c_int, ctypes.c_char_p, c_u64, c_vp,
                                c_u64]),
+    "s3dg_npz_archive_size": (c_int, [ctypes.POINTER(NpzMember), c_u64, ctypes.POINTER(c_u64)]),
+    "s3dg_npz_frame_batch": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(NpzArchive), c_u64, ctypes.POINTER(NpzMember), c_u64,
+                                     c_vp, c_u64, c_vp]),
+    "s3dg_npz_check_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(NpzArchive), c_u64, ctypes.POINTER(NpzMember), c_u64,
+                                     c_vp, c_u64, c_vp, ctypes.POINTER(NpzRec), ctypes.POINTER(NpzRec)]),
     "s3dg_device_alloc": (c_int, [c_vp, c_u64, ctypes.POINTER(c_vp)]),
     "s3dg_device_free": (c_int, [c_vp, c_vp]),
     "s3dg_host_alloc_pinned": (c_int, [c_u64, ctypes.POINTER(c_vp)]),

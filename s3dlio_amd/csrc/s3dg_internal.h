@@ -16,6 +16,7 @@
 #include "s3dg_tfrecord_var_plan.h" // TfvCounts, the per-record table
 #include "s3dg_tfrecord_search_plan.h" // TfsPlanA, TfsPlanB: the search's workspaces
 #include "s3dg_tfrecord_extract_plan.h" // TfxCounts, TfxLayout: the extract's workspace
+#include "s3dg_npz_plan.h"          // NpzCounts, NpzLayout: the NPZ batch's workspace
 #include "s3dg_prefix.h"            // PrefixParams and the one function that makes them
 
 // Sets the calling thread's error text (s3dg_last_error) and returns code.
@@ -426,6 +427,13 @@ hipError_t tfrecord_search_resolve(const uint8_t *base, uint8_t *idx, const uint
 hipError_t tfrecord_extract_launch(const uint8_t *src, const uint8_t *idx, uint8_t *dst, uint8_t *ws, const TfxLayout &L,
                                    const TfxCounts &C, uint64_t n, size_t scan_tmp_bytes, void *tab_dev, int cus,
                                    hipEvent_t *marks, hipStream_t s);
+// NPZ archives framed or checked (s3dg_npz_batch.hip; s3dg_npz_plan.h).  ws is
+// the workspace of npz_layout with npz_build's bytes uploaded and, for a check,
+// the results reset.  frame: src -> base; check: base is only read and the
+// findings go to the results.  One launch over the regions (none when every
+// member is empty), one wave per member behind it.
+hipError_t npz_batch_launch(bool frame, const uint8_t *src, uint8_t *base, uint8_t *ws, const NpzLayout &L,
+                            const NpzCounts &C, void *tab_dev, int cus, hipStream_t s);
 
 // ---- NUMA placement of host buffers (s3dg_numa.cpp) -------------------------
 bool device_local_cpus(int device, cpu_set_t *out);

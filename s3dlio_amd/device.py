@@ -355,6 +355,93 @@ class TfRecordExtract:
                    int(r.bad_length_crc), int(r.bad_data_crc), None if ft == none else ft, None if fr == none else fr, takes)
 
 
+NPZ_STYLE_RAW, NPZ_STYLE_LEGACY = 0, 1
+
+
+@dataclass(frozen=True)
+class NpzResult:
+    """What Context.npz_check_batch found (s3dg_npz_result): the totals over
+    the archives and, unless it was called with per_archive=False, the bad
+    archives as (index, NpzResult) pairs."""
+    members: int = 0              # members looked at
+    bad_members: int = 0          # members bad in at least one of the next two
+    bad_local: int = 0            # local header, name or NPY header differ from the descriptor's
+    bad_crc: int = 0              # the local header's CRC field is not the CRC-32 of NPY header + payload in memory
+    bad_directory: int = 0        # archives whose central directory or end record differ
+    first_archive: int | None = None   # index of the first bad archive; None = clean
+    first_member: int | None = None    # its lowest bad member; None when clean or when only the directory is bad
+    archives: tuple | None = None
+
+    @property
+    def ok(self) -> bool:
+        return self.bad_members == 0 and self.bad_directory == 0
+
+    @classmethod
+    def _of(cls, r, archives=None) -> "NpzResult":
+        none = 2**64 - 1
+        fa, fm = int(r.first_archive), int(r.first_member)
+        return cls(int(r.members), int(r.bad_members), int(r.bad_local), int(r.bad_crc), int(r.bad_directory),
+                   None if fa == none else fa, None if fm == none else fm, archives)
+
+
+def _npz_members(members):
+    """(s3dg_npz_member array, count, blob) of members (name, npy_header_bytes, src_off_or_None, size)."""
+    rows = [tuple(m) for m in members]
+    if any(len(m) != 4 for m in rows):
+        raise ValueError("a member is (name, npy_header_bytes, src_off or None, size)")
+    arr = (_lib.NpzMember * max(1, len(rows)))()
+    blob = bytearray()
+    for j, (name, hdr, src_off, size) in enumerate(rows):
+        name = name.encode() if isinstance(name, str) else bytes(name)
+        hdr = bytes(hdr)
+        src_off, size = 2**64 - 1 if src_off is None else int(src_off), int(size)
+        if not (0 <= src_off < 2**64 and 0 <= size < 2**64):
+            raise ValueError("member fields must fit 64 unsigned bits")
+        if len(blob) + len(name) + len(hdr) >= 2**32:
+            raise ValueError("names and NPY headers of one call must stay below 2^32 bytes")
+        arr[j] = _lib.NpzMember(src_off, size, len(blob), len(name), len(blob) + len(name), len(hdr))
+        blob += name + hdr
+    return arr, len(rows), bytes(blob)
+
+
+def npz_archive_size(members, style: int = NPZ_STYLE_RAW) -> int:
+    """Bytes of the archive that Context.npz_frame_batch writes for these
+    members (name, npy_header_bytes, src_off_or_None, size): both styles take
+    the same room.  ValueError when the sum overflows 64 bits."""
+    arr, n, _ = _npz_members(members)
+    out = _lib.c_u64(0)
+    call("s3dg_npz_archive_size", arr, n, ctypes.byref(out))
+    return int(out.value)
+
+
+def _npz_archives(archives):
+    """(archive array, n, member array, members, blob, bytes of src and dst the archives reach)."""
+    rows, flat = [], []
+    for a in archives:
+        a = tuple(a)
+        if len(a) not in (2, 3):
+            raise ValueError("an archive is (dst_off, members[, style])")
+        ms = [tuple(m) for m in a[1]]
+        dst_off, style = int(a[0]), int(a[2]) if len(a) == 3 else NPZ_STYLE_RAW
+        if not (0 <= dst_off < 2**64 and 0 <= style < 2**32):
+            raise ValueError("archive fields must fit their unsigned fields")
+        rows.append((dst_off, len(flat), len(ms), style))
+        flat += ms
+    marr, nm, blob = _npz_members(flat)
+    arr = (_lib.NpzArchive * max(1, len(rows)))()
+    need_src = need_dst = 0
+    for k, (dst_off, m0, count, style) in enumerate(rows):
+        arr[k] = _lib.NpzArchive(dst_off, m0, count, style, 0)
+        total = 22
+        for j in range(m0, m0 + count):
+            m = marr[j]
+            total += 30 + m.hdr_len + m.size + 46 + 2 * m.name_len
+            if m.src_off != 2**64 - 1 and m.size:
+                need_src = max(need_src, m.src_off + m.size)
+        need_dst = max(need_dst, dst_off + total)
+    return arr, len(rows), marr, nm, blob, need_src, need_dst
+
+
 def _tfr_lengths(lengths) -> np.ndarray:
     """Any integer sequence or numpy array as a contiguous uint64 array."""
     if isinstance(lengths, np.ndarray):
@@ -1207,6 +1294,41 @@ class Context:
         call("s3dg_tfrecord_extract_batch", self._h, self._src(src, need_src), self._src(index, need_idx),
              self._dst(dst, need_dst), arr, n, self._s(stream), ctypes.byref(tot), per)
         return TfRecordExtract._of(tot, tuple(TfRecordExtract._of(per[k]) for k in range(n)) if per_take else None)
+
+    # -- NPZ archives framed and checked in HBM -----------------------------------------
+    def npz_frame_batch(self, src, dst, archives, stream=None) -> None:
+        """Writes every archive of the list into dst in one device call
+        (DESIGN.md §5.5.5).  An archive is (dst_off, members[, style]); a
+        member is (name, npy_header_bytes, src_off_or_None, size): `size`
+        payload bytes at src + src_off, or zeros for None, stored under
+        `name` (".npy" included) behind the given NPY header (npy_header,
+        npy_header_u1; b"" stores a raw file).  style NPZ_STYLE_RAW (default)
+        gives generate_npz_bytes' header fields, NPZ_STYLE_LEGACY build_npz's.
+        dst_off and src_off are multiples of 16; archives may come in any
+        order and share sources, and must not overlap each other or a source.
+        There is no ZIP64: an archive of 4 GiB or more is refused.  The spans
+        are checked against the tensors' sizes before any launch (ValueError).
+        Ordered on `stream`; returns without waiting."""
+        arr, n, marr, nm, blob, need_src, need_dst = _npz_archives(archives)
+        call("s3dg_npz_frame_batch", self._h, self._src(src, need_src), self._dst(dst, need_dst), arr, n, marr, nm,
+             ctypes.cast(ctypes.c_char_p(blob), c_vp), len(blob), self._s(stream))
+
+    def npz_check_batch(self, src, archives, stream=None, per_archive: bool = True) -> NpzResult:
+        """The read-side twin of npz_frame_batch over the same archives, found
+        at src + dst_off (a member's src_off is not used).  Per member the
+        local header, name and NPY header against the descriptors and the CRC
+        field against the CRC-32 of NPY header and payload in memory; per
+        archive the central directory and the end record.  Synchronous on
+        `stream`; writes nothing.  per_archive=False asks for the totals only."""
+        arr, n, marr, nm, blob, _, need = _npz_archives(archives)
+        tot = _lib.NpzRec(0, 0, 0, 0, 0, 2**64 - 1, 2**64 - 1)
+        per = (_lib.NpzRec * max(1, n))() if per_archive else None
+        call("s3dg_npz_check_batch", self._h, self._src(src, need), arr, n, marr, nm,
+             ctypes.cast(ctypes.c_char_p(blob), c_vp), len(blob), self._s(stream), ctypes.byref(tot), per)
+        bad = None
+        if per_archive:
+            bad = tuple((k, NpzResult._of(per[k])) for k in range(n) if per[k].bad_members or per[k].bad_directory)
+        return NpzResult._of(tot, bad)
 
     def _tfrecord_walks(self, sym, src, streams, index, stream) -> list:
         rows = [tuple(int(x) for x in st) for st in streams]

@@ -48,6 +48,26 @@ def generate_npz_bytes(shape, dtype: str = "<f4", num_samples: int = 1):
     return hostbuf.readonly(out)
 
 
+def npy_header(shape, dtype: str = "<f4") -> bytes:
+    """build_npy_header_typed (src/data_formats/npz.rs:216-241): the NPY 1.0
+    header of an array, padded to a multiple of 64 bytes; what
+    generate_npz_bytes puts in front of x.npy and y.npy."""
+    dims = [int(d) for d in shape]
+    tup = "(" + ", ".join(str(d) for d in dims) + (",)" if len(dims) == 1 else ")")
+    d = "{'descr': '" + dtype + "', 'fortran_order': False, 'shape': " + tup + ", }"
+    hl = len(d) + 1
+    pad = (64 - ((6 + 2 + 2 + hl) % 64)) % 64
+    return b"\x93NUMPY\x01\x00" + (hl + pad).to_bytes(2, "little") + d.encode() + b" " * pad + b"\n"
+
+
+def npy_header_u1(n: int) -> bytes:
+    """make_npy_header (npz.rs:92-109): '|u1', shape (n,), padded to 16 bytes;
+    what build_npz puts in front of data.npy."""
+    d = "{'descr': '|u1', 'fortran_order': False, 'shape': (" + str(int(n)) + ",)}"
+    d += " " * ((16 - (10 + len(d) + 1) % 16) % 16) + "\n"
+    return b"\x93NUMPY\x01\x00" + len(d).to_bytes(2, "little") + d.encode()
+
+
 def crc32_device(ctx: Context, dst, nbytes: int | None = None, stream=None) -> int:
     """CRC-32 (IEEE) of a device buffer, computed on the GPU."""
     n = int(dst.numel() * dst.element_size()) if nbytes is None else nbytes
