@@ -1180,6 +1180,106 @@ int s3dg_npz_frame_batch(s3dg_ctx *ctx, const void *src_base, void *dst_base, co
 int s3dg_npz_check_batch(s3dg_ctx *ctx, const void *base, const s3dg_npz_archive *archives, uint64_t n,
                          const s3dg_npz_member *members, uint64_t nmembers, const uint8_t *blob, uint64_t blob_len,
                          void *stream, s3dg_npz_result *total, s3dg_npz_result *per_archive);
+/* ---- NPZ archives unpacked on the device from their bytes ----
+ * list_npz_arrays / read_npz_array (src/data_formats/npz.rs) for every archive
+ * of a list in one call each: the index of stored ZIP archives nobody has
+ * described (numpy.savez's included), and their members' array bytes copied
+ * out by that index with the CRC-32 checked in the copy.  Everything an
+ * archive says about itself is read on the device.
+ * Archive k is `bytes` bytes at base + off (any byte offset; no byte outside is
+ * read).  Per member, in central-directory order and at most max_members of
+ * them, one 32-byte entry of eight little-endian uint32 goes to
+ * table + tab_off (a multiple of 16), every offset from the archive's first
+ * byte: local_off, name_len | flags << 16, hdr_off (first byte of the stored
+ * file: the NPY magic when there is one), hdr_len, data_off, size, crc, 0.
+ * hdr_off + hdr_len == data_off; the stored file is hdr_len + size bytes; the
+ * name is at local_off + 30. */
+typedef struct {
+    uint64_t off, bytes, tab_off, max_members;
+} s3dg_npz_stream;
+enum { S3DG_NPZ_WALK_OK = 0,
+       S3DG_NPZ_WALK_NO_END = 1,         /* no end record whose comment reaches the archive's end in the last 22 + 65535 bytes */
+       S3DG_NPZ_WALK_DIRECTORY = 2,      /* the end record or a central entry is inconsistent, or a member leaves [0, cd_off) */
+       S3DG_NPZ_WALK_LOCAL = 3,          /* a local header disagrees with its central entry */
+       S3DG_NPZ_WALK_UNSUPPORTED = 4,    /* a member is deflated, encrypted or has a data descriptor */
+       S3DG_NPZ_WALK_CAPPED = 5 };       /* max_members entries are written and more members follow */
+typedef struct {
+    uint64_t status;
+    uint64_t members;                    /* entries written; all of them valid whatever the status */
+    uint64_t members_total;              /* the end record's count (0 with NO_END) */
+    uint64_t payload_bytes;              /* sum of size over the entries written */
+    uint64_t packed_bytes;               /* sum of round_up(size, 16): what one take of all of them spans */
+    uint64_t bad_member;                 /* the member refused (DIRECTORY, LOCAL, UNSUPPORTED); UINT64_MAX when none or the end record */
+} s3dg_npz_walk_result;
+/* Synchronous on `stream`; results is a host array of n.  One wave walks one
+ * archive.  End record: searched backwards from the end, 64 positions a step,
+ * for the signature with comment_len equal to the distance to the archive's
+ * end; the hit nearest the end wins.  Directory: disk numbers 0, equal entry
+ * counts, cd_off + cd_size at the end record, no ZIP64 marker, every central
+ * entry with its signature inside the directory, the entries ending exactly at
+ * its end, every stored file inside [0, cd_off).  Local header: signature,
+ * name, flags, method and CRC field equal to the central entry's, both sizes
+ * equal to it or 0xFFFFFFFF with the real values in the extra field's 0x0001
+ * record (numpy.savez); the data starts behind the local header's own name and
+ * extra lengths.  NPY preamble: "\x93NUMPY", major 1 with a u16 or major 2 / 3
+ * with a u32 header length; hdr_len is preamble plus that, inside the stored
+ * file and at most 65535, anything else is a raw stored file of hdr_len 0.
+ * Refusals (S3DG_EINVAL, before anything is reserved or enqueued): "null
+ * context", "null base", "null table", "null results", "null archive array", a
+ * misaligned table, more than 2^32 - 1 archives, and per archive ("archive k:
+ * ...") tab_off no multiple of 16, an archive of 2^32 bytes or more, an end
+ * address overflowing.  n == 0 succeeds whatever the other pointers. */
+int s3dg_npz_index_batch(s3dg_ctx *ctx, const void *base, void *table, const s3dg_npz_stream *archives, uint64_t n,
+                         void *stream, s3dg_npz_walk_result *results);
+/* A take is members [first, first + count) of the table at table + tab_off,
+ * read from the archive at base + off; a take of count == 1 is a pick, B of
+ * them with dst_off = k * row_stride gather one array out of each of B
+ * archives into rows.  Takes may come in any order, repeat, share an archive
+ * and have count == 0. */
+typedef struct {
+    uint64_t off, bytes;                 /* the archive, as s3dg_npz_stream */
+    uint64_t tab_off;                    /* its entries, as s3dg_npz_index_batch writes them (multiple of 16) */
+    uint64_t first, count;
+    uint64_t dst_off;                    /* member i lands at dst_base + dst_off (multiple of 16) + sum of round_up(size_j, 16), j < i */
+    uint64_t dst_cap;                    /* bytes that may be written there */
+} s3dg_npz_take;
+enum { S3DG_NPZ_TAKE_TAKEN = 0, S3DG_NPZ_TAKE_CAPACITY = 1, S3DG_NPZ_TAKE_TABLE = 2 };
+typedef struct {
+    uint64_t members, bytes;             /* members taken, payload bytes written */
+    uint64_t span;                       /* the packed span, padding included: taken and CAPACITY takes */
+    uint64_t status;                     /* 0 taken; 1 span exceeds dst_cap; 2 the entries do not describe the archive */
+    uint64_t bad_crc;                    /* copied members whose CRC-32 over NPY header || payload differs from the entry's */
+    uint64_t first_take, first_member;   /* first take with such a member and its lowest (numbered as in its table); UINT64_MAX when clean */
+} s3dg_npz_unpack_result;
+/* s3dg_tfrecord_extract_batch's contract.  Synchronous on `stream`; `takes` is
+ * consumed before it returns; per_take (a host array of n) may be NULL.  The
+ * entries are validated on the device before anything of the take is copied:
+ * local_off + 30 + name_len <= hdr_off, hdr_off + hdr_len == data_off,
+ * hdr_len <= 65535, data_off + size <= bytes, no wrap.  A take that fails is
+ * status 2: it reads no archive byte and writes nothing.  A take whose span
+ * exceeds dst_cap is status 1 and writes nothing; other takes are unaffected.
+ * A taken take writes exactly the payload bytes, each once; the padding
+ * between members is not written.  Reads are aligned dwords, each holding a
+ * byte of the stored file it serves.  A member whose CRC is wrong is delivered
+ * as it stands and counted.  A clean call costs no atomic beyond one per
+ * member longer than a region.  total sums the takes; its status is the
+ * maximum over them.  Scratch: 64 bytes per take and 36 bytes per member, kept
+ * with the stream's state.  Refusals (S3DG_EINVAL, before anything is reserved
+ * or enqueued): "null context", "null base", "null table", "null dst_base",
+ * "null output", "null take array", a misaligned table or dst_base, more than
+ * 2^32 - 1 takes, and per take ("take k: ...") tab_off or dst_off no multiple
+ * of 16, first + count, off + bytes, dst_off + dst_cap or the table's end
+ * overflowing, more than 2^31 - 2 members in one call, more than 2^46 archive
+ * bytes in one call (a take counts min(count * bytes, dst_cap + 65535 count),
+ * what it can read).  n == 0 succeeds whatever the other pointers. */
+int s3dg_npz_unpack_batch(s3dg_ctx *ctx, const void *base, const void *table, void *dst_base, const s3dg_npz_take *takes,
+                          uint64_t n, void *stream, s3dg_npz_unpack_result *total, s3dg_npz_unpack_result *per_take);
+/* The same call with its passes timed by device events: pass_ms[3] gets the
+ * milliseconds of the plan (validation, offsets and constants), the scan of
+ * the regions, and the copy with its fold ("null pass_ms"). */
+int s3dg_npz_unpack_timed(s3dg_ctx *ctx, const void *base, const void *table, void *dst_base, const s3dg_npz_take *takes,
+                          uint64_t n, void *stream, s3dg_npz_unpack_result *total, s3dg_npz_unpack_result *per_take,
+                          float *pass_ms);
 
 /* ---- streaming generator (DataGenerator / ObjectGen / PyO3 Generator) ----- */
 /* One object of `size` bytes in the DG1 layout, generated on a host slot's

@@ -8,11 +8,12 @@ the library is absent (no CPU fallback exists).
 from ._lib import S3dgError, lib  # noqa: F401  (loads libs3dlio_amd.so)
 from .hostbuf import BytesView  # noqa: F401
 from .device import (BLOCK_SIZE, DEFAULT_BASE_SEED, BatchVerifyResult, ChunkResult, Chunker, Context, LzMeasure,  # noqa: F401
-                     LzResult, Measure, MeasureResult, NPZ_STYLE_LEGACY, NPZ_STYLE_RAW, NpzResult, ReduceResult, Reducer,
+                     LzResult, Measure, MeasureResult, NPZ_STYLE_LEGACY, NPZ_STYLE_RAW, NpzEntry, NpzResult, NpzUnpack, NpzWalk, ReduceResult,
+                     Reducer,
                      TfRecordExtract, TfRecordResult, TfRecordWalk,
                      VerifyResult,
                      chunks_search_geometry, compress_ratio,
-                     device_count, host_context, host_slots, npz_archive_size, object_entropy, parse_devices,
+                     device_count, host_context, host_slots, npz_archive_size, npz_entries, object_entropy, parse_devices,
                      reduce_geometry,
                      tfrecord_index_text,
                      tfrecord_search_geometry, tfrecord_size, tfrecord_var_size, unique_blocks, xoshiro_jump)

@@ -115,6 +115,29 @@ class NpzRec(ctypes.Structure):
                 ("bad_directory", c_u64), ("first_archive", c_u64), ("first_member", c_u64)]
 
 
+class NpzStream(ctypes.Structure):
+    """s3dg_npz_stream"""
+    _fields_ = [("off", c_u64), ("bytes", c_u64), ("tab_off", c_u64), ("max_members", c_u64)]
+
+
+class NpzWalkRec(ctypes.Structure):
+    """s3dg_npz_walk_result"""
+    _fields_ = [("status", c_u64), ("members", c_u64), ("members_total", c_u64), ("payload_bytes", c_u64),
+                ("packed_bytes", c_u64), ("bad_member", c_u64)]
+
+
+class NpzTake(ctypes.Structure):
+    """s3dg_npz_take"""
+    _fields_ = [("off", c_u64), ("bytes", c_u64), ("tab_off", c_u64), ("first", c_u64), ("count", c_u64),
+                ("dst_off", c_u64), ("dst_cap", c_u64)]
+
+
+class NpzUnpackRec(ctypes.Structure):
+    """s3dg_npz_unpack_result"""
+    _fields_ = [("members", c_u64), ("bytes", c_u64), ("span", c_u64), ("status", c_u64), ("bad_crc", c_u64),
+                ("first_take", c_u64), ("first_member", c_u64)]
+
+
 class MeasureRec(ctypes.Structure):
     """s3dg_measure_result"""
     _fields_ = [("bytes", c_u64), ("zero_bytes", c_u64), ("blocks", c_u64), ("unique_blocks", c_u64),
@@ -294,6 +317,12 @@ SIGNATURES = {
                                      c_vp, c_u64, c_vp]),
     "s3dg_npz_check_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(NpzArchive), c_u64, ctypes.POINTER(NpzMember), c_u64,
                                      c_vp, c_u64, c_vp, ctypes.POINTER(NpzRec), ctypes.POINTER(NpzRec)]),
+    "s3dg_npz_index_batch": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(NpzStream), c_u64, c_vp, ctypes.POINTER(NpzWalkRec)]),
+    "s3dg_npz_unpack_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(NpzTake), c_u64, c_vp,
+                                      ctypes.POINTER(NpzUnpackRec), ctypes.POINTER(NpzUnpackRec)]),
+    "s3dg_npz_unpack_timed": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(NpzTake), c_u64, c_vp,
+                                      ctypes.POINTER(NpzUnpackRec), ctypes.POINTER(NpzUnpackRec),
+                                      ctypes.POINTER(ctypes.c_float)]),
     "s3dg_device_alloc": (c_int, [c_vp, c_u64, ctypes.POINTER(c_vp)]),
     "s3dg_device_free": (c_int, [c_vp, c_vp]),
     "s3dg_host_alloc_pinned": (c_int, [c_u64, ctypes.POINTER(c_vp)]),

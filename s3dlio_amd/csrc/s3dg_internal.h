@@ -17,6 +17,7 @@
 #include "s3dg_tfrecord_search_plan.h" // TfsPlanA, TfsPlanB: the search's workspaces
 #include "s3dg_tfrecord_extract_plan.h" // TfxCounts, TfxLayout: the extract's workspace
 #include "s3dg_npz_plan.h"          // NpzCounts, NpzLayout: the NPZ batch's workspace
+#include "s3dg_npz_unpack_plan.h"   // NzuCounts, NzuLayout: the NPZ unpack's workspace
 #include "s3dg_prefix.h"            // PrefixParams and the one function that makes them
 
 // Sets the calling thread's error text (s3dg_last_error) and returns code.
@@ -434,6 +435,19 @@ hipError_t tfrecord_extract_launch(const uint8_t *src, const uint8_t *idx, uint8
 // member is empty), one wave per member behind it.
 hipError_t npz_batch_launch(bool frame, const uint8_t *src, uint8_t *base, uint8_t *ws, const NpzLayout &L,
                             const NpzCounts &C, void *tab_dev, int cus, hipStream_t s);
+// NPZ archives indexed from their bytes and unpacked by that index
+// (s3dg_npz_unpack.hip; s3dg_npz_unpack_plan.h).  The walk: one wave per
+// archive, descriptors and results in device memory.  The unpack: ws is the
+// workspace of nzu_layout with nzu_build's bytes uploaded and the results
+// reset; the plan pass, three sums (tfrecord_search_scan), the copy-and-hash
+// launch over the host's bound of regions and, when the call can have long
+// members, a thread per such member.  The events (nullable, 4) are recorded at
+// the start and behind the plan, the regions' scan, and the copy with its fold.
+hipError_t npz_index_launch(const uint8_t *base, uint8_t *table, const s3dg_npz_stream *arch_dev, uint64_t n,
+                            s3dg_npz_walk_result *res_dev, hipStream_t s);
+hipError_t npz_unpack_launch(const uint8_t *src, const uint8_t *tab, uint8_t *dst, uint8_t *ws, const NzuLayout &L,
+                             const NzuCounts &C, uint64_t n, size_t scan_tmp_bytes, void *tab_dev, int cus, hipEvent_t *marks,
+                             hipStream_t s);
 
 // ---- NUMA placement of host buffers (s3dg_numa.cpp) -------------------------
 bool device_local_cpus(int device, cpu_set_t *out);

@@ -12,6 +12,7 @@ the entropy and base block made explicit.
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 from dataclasses import dataclass
 from fractions import Fraction
 
@@ -382,6 +383,69 @@ class NpzResult:
         fa, fm = int(r.first_archive), int(r.first_member)
         return cls(int(r.members), int(r.bad_members), int(r.bad_local), int(r.bad_crc), int(r.bad_directory),
                    None if fa == none else fa, None if fm == none else fm, archives)
+
+
+_NPZ_WALK_STATUS = ("complete", "no_end", "directory", "local", "unsupported", "capped")
+
+
+@dataclass(frozen=True)
+class NpzWalk:
+    """What Context.npz_index_batch found in one archive (s3dg_npz_walk_result)."""
+    status: str = "complete"      # "complete" | "no_end" | "directory" | "local" | "unsupported" | "capped" (max_members reached)
+    members: int = 0              # entries written; all of them valid whatever the status
+    members_total: int = 0        # the end record's count
+    payload_bytes: int = 0        # sum of size over the entries written
+    packed_bytes: int = 0         # sum of round_up(size, 16): what one take of all of them spans
+    bad_member: int | None = None     # the member refused ("directory", "local", "unsupported")
+
+    @property
+    def ok(self) -> bool:
+        return self.status == "complete"
+
+    @classmethod
+    def _of(cls, r) -> "NpzWalk":
+        bm = int(r.bad_member)
+        return cls(_NPZ_WALK_STATUS[int(r.status)], int(r.members), int(r.members_total), int(r.payload_bytes),
+                   int(r.packed_bytes), None if bm == 2**64 - 1 else bm)
+
+
+NpzEntry = namedtuple("NpzEntry", "local_off name_len flags hdr_off hdr_len data_off size crc")
+NpzEntry.__doc__ = "One member as Context.npz_index_batch describes it; every offset from the archive's first byte."
+
+
+def npz_entries(table, tab_off: int, count: int) -> list:
+    """Entries [0, count) of the table at table + tab_off, copied back, as NpzEntry tuples."""
+    raw = table[tab_off:tab_off + 32 * count].cpu().numpy().view("<u4").reshape(-1, 8)
+    return [NpzEntry(int(e[0]), int(e[1]) & 0xFFFF, int(e[1]) >> 16, *(int(x) for x in e[2:7])) for e in raw]
+
+
+_UNPACK_STATUS = ("taken", "capacity", "table")
+
+
+@dataclass(frozen=True)
+class NpzUnpack:
+    """What Context.npz_unpack_batch did (s3dg_npz_unpack_result): the totals
+    over the takes and, unless it was called with per_take=False, one NpzUnpack
+    per take."""
+    members: int = 0              # members of the takes that were taken
+    bytes: int = 0                # payload bytes written
+    span: int = 0                 # packed span, padding included
+    status: str = "taken"         # "taken" | "capacity" (span exceeds dst_cap) | "table" (entries do not describe the archive)
+    bad_crc: int = 0              # copied members whose CRC-32 differs from the entry's
+    first_take: int | None = None     # index of the first take with such a member; None = clean
+    first_member: int | None = None   # its lowest bad member, numbered as in its table
+    takes: tuple | None = None
+
+    @property
+    def ok(self) -> bool:
+        return self.status == "taken" and self.bad_crc == 0
+
+    @classmethod
+    def _of(cls, r, takes=None) -> "NpzUnpack":
+        none = 2**64 - 1
+        ft, fm = int(r.first_take), int(r.first_member)
+        return cls(int(r.members), int(r.bytes), int(r.span), _UNPACK_STATUS[int(r.status)], int(r.bad_crc),
+                   None if ft == none else ft, None if fm == none else fm, takes)
 
 
 def _npz_members(members):
@@ -1329,6 +1393,83 @@ class Context:
         if per_archive:
             bad = tuple((k, NpzResult._of(per[k])) for k in range(n) if per[k].bad_members or per[k].bad_directory)
         return NpzResult._of(tot, bad)
+
+    # -- NPZ archives unpacked from their bytes ------------------------------------------
+    def npz_index_batch(self, src, archives, table, stream=None) -> list:
+        """The members of stored ZIP archives nobody has described
+        (numpy.savez's included), in one device call.  Each
+        archive is (off, nbytes, tab_off, max_members): nbytes at src + off
+        (any byte offset) gets one 32-byte entry per member, at most
+        max_members of them, at table + tab_off (a multiple of 16);
+        npz_entries reads them back.  End record, central directory, local
+        headers and NPY preambles are all read and judged on the device.
+        Synchronous on `stream`.  Returns an NpzWalk per archive."""
+        rows = [tuple(int(x) for x in a) for a in archives]
+        if any(len(a) != 4 for a in rows):
+            raise ValueError("an archive is (off, nbytes, tab_off, max_members)")
+        if any(x < 0 or x >= 2**64 for a in rows for x in a):
+            raise ValueError("archive fields must fit 64 unsigned bits")
+        n = len(rows)
+        arr = (_lib.NpzStream * max(1, n))()
+        need_src = need_tab = 0
+        for k, (off, nbytes, tab_off, cap) in enumerate(rows):
+            arr[k] = _lib.NpzStream(off, nbytes, tab_off, cap)
+            need_src = max(need_src, off + nbytes)
+            need_tab = max(need_tab, tab_off + 32 * min(cap, 65535))
+        res = (_lib.NpzWalkRec * max(1, n))()
+        call("s3dg_npz_index_batch", self._h, self._src(src, need_src), self._dst(table, need_tab), arr, n, self._s(stream), res)
+        return [NpzWalk._of(res[k]) for k in range(n)]
+
+    def npz_unpack_batch(self, src, table, dst, takes, stream=None, per_take: bool = True) -> NpzUnpack:
+        """The array bytes of indexed members out of their archives in one
+        device call, every copied member's CRC-32 (NPY header and payload)
+        checked in the copy.  Each take is (off, bytes, tab_off, first, count,
+        dst_off, dst_cap): of the archive of `bytes` at src + off whose
+        entries npz_index_batch left at table + tab_off, members [first,
+        first + count) go to dst + dst_off, each at the next multiple of 16,
+        at most dst_cap bytes (NpzWalk.packed_bytes for a whole archive); the
+        padding is not written.  B takes of count 1 gather one array out of
+        each of B archives into rows.  tab_off and dst_off are multiples of
+        16; takes may come in any order, repeat, share an archive and be
+        empty.  The entries are validated on the device first: a take whose
+        entries leave its archive ("table") or whose span exceeds dst_cap
+        ("capacity") writes nothing, the others are unaffected.  A member
+        with a wrong CRC is delivered as it stands and counted.  Spans are
+        checked against the tensors' sizes before any launch (ValueError).
+        Synchronous on `stream`; per_take=False asks for the totals only."""
+        rows = [tuple(int(x) for x in tk) for tk in takes]
+        if any(len(tk) != 7 for tk in rows):
+            raise ValueError("a take is (off, bytes, tab_off, first, count, dst_off, dst_cap)")
+        if any(x < 0 or x >= 2**64 for tk in rows for x in tk):
+            raise ValueError("take fields must fit 64 unsigned bits")
+        n = len(rows)
+        arr = (_lib.NpzTake * max(1, n))()
+        need_src = need_tab = need_dst = 0
+        for k, tk in enumerate(rows):
+            arr[k] = _lib.NpzTake(*tk)
+            off, nbytes, tab_off, first, count, dst_off, dst_cap = tk
+            need_src = max(need_src, off + nbytes)
+            need_tab = max(need_tab, tab_off + 32 * (first + count))
+            need_dst = max(need_dst, dst_off + dst_cap)
+        tot = _lib.NpzUnpackRec(0, 0, 0, 0, 0, 2**64 - 1, 2**64 - 1)
+        per = (_lib.NpzUnpackRec * max(1, n))() if per_take else None
+        call("s3dg_npz_unpack_batch", self._h, self._src(src, need_src), self._src(table, need_tab),
+             self._dst(dst, need_dst), arr, n, self._s(stream), ctypes.byref(tot), per)
+        return NpzUnpack._of(tot, tuple(NpzUnpack._of(per[k]) for k in range(n)) if per_take else None)
+
+    def npz_list(self, src, off: int, nbytes: int, stream=None) -> list:
+        """list_npz_arrays for one archive of nbytes at src + off: [(name,
+        npy_header_bytes, size)] in directory order, names as stored.
+        ValueError when the archive cannot be walked."""
+        t = _lib.torch
+        table = t.empty(32 * 65535, dtype=t.uint8, device=f"cuda:{self.device}")
+        w = self.npz_index_batch(src, [(off, nbytes, 0, 65535)], table, stream=stream)[0]
+        if not w.ok:
+            raise ValueError(f"npz_list: {w.status}" + ("" if w.bad_member is None else f" at member {w.bad_member}"))
+        def grab(lo, hi):
+            return src[off + lo:off + hi].cpu().numpy().tobytes()
+        return [(grab(e.local_off + 30, e.local_off + 30 + e.name_len), grab(e.hdr_off, e.data_off), e.size)
+                for e in npz_entries(table, 0, w.members)]
 
     def _tfrecord_walks(self, sym, src, streams, index, stream) -> list:
         rows = [tuple(int(x) for x in st) for st in streams]
