@@ -1281,6 +1281,84 @@ int s3dg_npz_unpack_timed(s3dg_ctx *ctx, const void *base, const void *table, vo
                           uint64_t n, void *stream, s3dg_npz_unpack_result *total, s3dg_npz_unpack_result *per_take,
                           float *pass_ms);
 
+/* ---- DEFLATE streams and compressed NPZ members inflated on the device ----
+ * RFC 1951 inflate, one wave per stream: raw DEFLATE (no zlib or gzip wrapper)
+ * of src_bytes bytes at src_base + src_off (any byte offset; no byte outside
+ * is used) is decoded to dst_base + dst_off (a multiple of 16), at most
+ * dst_cap bytes.  want_bytes is the size the output must have, or UINT64_MAX
+ * for any; crc is the CRC-32 the output must have when flags bit 0 is set.
+ * Items may come in any order, repeat and share a source; two items must not
+ * share destination bytes. */
+typedef struct {
+    uint64_t src_off, src_bytes;
+    uint64_t dst_off, dst_cap;
+    uint64_t want_bytes;
+    uint32_t crc, flags;
+} s3dg_inflate_item;
+enum { S3DG_INFLATE_CRC = 1 };           /* flags bit 0: crc is given */
+enum { S3DG_INFLATE_OK = 0,
+       S3DG_INFLATE_CAPACITY = 1,        /* the output would pass dst_cap */
+       S3DG_INFLATE_SIZE = 2,            /* the stream ended cleanly with fewer bytes than want_bytes, or would pass it */
+       S3DG_INFLATE_TRUNCATED = 3,       /* the input ran out before the final block ended */
+       S3DG_INFLATE_BAD_STREAM = 4 };    /* the bytes are no DEFLATE stream (the rules below) */
+typedef struct {
+    uint64_t status;                     /* total: the maximum over the items */
+    uint64_t out_bytes;                  /* bytes written; of a failed item, what it had delivered before it stopped */
+    uint64_t in_bytes;                   /* input bytes consumed, the last one possibly in part; trailing input is no error */
+    uint64_t bad_crc;                    /* OK items with S3DG_INFLATE_CRC whose output's CRC-32 differs */
+    uint64_t first_item;                 /* the first item whose status is not OK or whose CRC differs; UINT64_MAX when clean */
+} s3dg_inflate_result;
+/* Synchronous on `stream`; `items` is consumed before it returns; per_item (a
+ * host array of n) may be NULL.  An item that fails ends with its status and
+ * leaves the others untouched; what it had already written stays inside
+ * [dst_off, dst_off + dst_cap), and no byte outside that place is ever
+ * written.  BAD_STREAM: block type 3; a stored block whose LEN is not ~NLEN;
+ * HLIT above 286 or HDIST above 30; a code-length repeat that runs over the
+ * set or a 16 with no length before it; no end-of-block code; a set of code
+ * lengths that is over-subscribed, or incomplete unless it is one code of
+ * length 1 (zlib's rule; the code-length code must be complete); a bit
+ * pattern that is no code; length symbols 286 and 287, distance codes 30 and
+ * 31; a distance that reaches in front of the output's first byte.  A
+ * condition that the missing input could still have met is TRUNCATED.  The
+ * CRC-32 is computed from the finished output by a second kernel of the same
+ * call.  Refusals (S3DG_EINVAL, before anything is reserved or enqueued):
+ * "null context", "null src_base", "null dst_base", "null output", "null item
+ * array", a misaligned dst_base, more than 2^32 - 1 items, and per item ("item
+ * k: ...") dst_off no multiple of 16, src_off + src_bytes or dst_off +
+ * dst_cap overflowing, flags beyond bit 0.  n == 0 succeeds whatever the
+ * other pointers. */
+int s3dg_inflate_batch(s3dg_ctx *ctx, const void *src_base, void *dst_base, const s3dg_inflate_item *items, uint64_t n,
+                       void *stream, s3dg_inflate_result *total, s3dg_inflate_result *per_item);
+/* s3dg_npz_index_batch for archives whose members are stored or deflated:
+ * its arguments, results, walk and refusals, except that method 8 with flags
+ * clear of bits 0 and 3 is accepted beside method 0 (csize == usize is asked
+ * of method 0 only).  A deflated member's NPY header lies inside its
+ * compressed stream, so a z entry describes the whole stored file: eight
+ * little-endian uint32 local_off, name_len | flags << 16, data_off (first
+ * byte of the member's data), csize, usize, crc, method, 0.  payload_bytes and
+ * packed_bytes are sums over usize and round_up(usize, 16). */
+int s3dg_npz_zindex_batch(s3dg_ctx *ctx, const void *base, void *table, const s3dg_npz_stream *archives, uint64_t n,
+                          void *stream, s3dg_npz_walk_result *results);
+typedef struct {
+    uint64_t members, bytes;             /* members of taken takes; bytes their streams delivered */
+    uint64_t span;                       /* the packed span, padding included: taken and CAPACITY takes */
+    uint64_t status;                     /* as s3dg_npz_unpack_result */
+    uint64_t bad_crc;                    /* members delivered whole whose CRC-32 differs from the entry's */
+    uint64_t bad_stream;                 /* members whose inflate status is not OK or whose output is not usize bytes */
+    uint64_t first_take, first_member;   /* first take with a member of either kind and its lowest; UINT64_MAX when clean */
+} s3dg_npz_zunpack_result;
+/* s3dg_npz_unpack_batch over z entries: member i's whole stored file (NPY
+ * header and array bytes) lands at dst_off + sum of round_up(usize_j, 16),
+ * j < i; a stored member is copied, a deflated one inflated, by the same
+ * kernel.  A plan pass on the device, one thread per take, validates the
+ * entries (local_off + 30 + name_len <= data_off, data_off + csize <= bytes,
+ * method 0 with csize == usize or method 8, no wrap), sums the places and
+ * writes the work items, so no index crosses the bus.  TABLE and CAPACITY
+ * takes write nothing.  Refusals as s3dg_npz_unpack_batch, less the bound on
+ * archive bytes. */
+int s3dg_npz_zunpack_batch(s3dg_ctx *ctx, const void *base, const void *table, void *dst_base, const s3dg_npz_take *takes,
+                           uint64_t n, void *stream, s3dg_npz_zunpack_result *total, s3dg_npz_zunpack_result *per_take);
+
 /* ---- streaming generator (DataGenerator / ObjectGen / PyO3 Generator) ----- */
 /* One object of `size` bytes in the DG1 layout, generated on a host slot's
  * GPU (taken round-robin at creation) and streamed into host buffers.  has_seed=0: time + counter

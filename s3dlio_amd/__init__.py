@@ -8,6 +8,8 @@ the library is absent (no CPU fallback exists).
 from ._lib import S3dgError, lib  # noqa: F401  (loads libs3dlio_amd.so)
 from .hostbuf import BytesView  # noqa: F401
 from .device import (BLOCK_SIZE, DEFAULT_BASE_SEED, BatchVerifyResult, ChunkResult, Chunker, Context, LzMeasure,  # noqa: F401
+                     INFLATE_BAD_STREAM, INFLATE_CAPACITY, INFLATE_OK, INFLATE_SIZE, INFLATE_TRUNCATED, InflateResult, NpzZEntry,
+                     NpzZUnpack, npz_zentries,
                      LzResult, Measure, MeasureResult, NPZ_STYLE_LEGACY, NPZ_STYLE_RAW, NpzEntry, NpzResult, NpzUnpack, NpzWalk, ReduceResult,
                      Reducer,
                      TfRecordExtract, TfRecordResult, TfRecordWalk,

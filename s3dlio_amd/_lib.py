@@ -138,6 +138,23 @@ class NpzUnpackRec(ctypes.Structure):
                 ("first_take", c_u64), ("first_member", c_u64)]
 
 
+class InflateItem(ctypes.Structure):
+    """s3dg_inflate_item"""
+    _fields_ = [("src_off", c_u64), ("src_bytes", c_u64), ("dst_off", c_u64), ("dst_cap", c_u64), ("want_bytes", c_u64),
+                ("crc", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class InflateRec(ctypes.Structure):
+    """s3dg_inflate_result"""
+    _fields_ = [("status", c_u64), ("out_bytes", c_u64), ("in_bytes", c_u64), ("bad_crc", c_u64), ("first_item", c_u64)]
+
+
+class NpzZUnpackRec(ctypes.Structure):
+    """s3dg_npz_zunpack_result"""
+    _fields_ = [("members", c_u64), ("bytes", c_u64), ("span", c_u64), ("status", c_u64), ("bad_crc", c_u64),
+                ("bad_stream", c_u64), ("first_take", c_u64), ("first_member", c_u64)]
+
+
 class MeasureRec(ctypes.Structure):
     """s3dg_measure_result"""
     _fields_ = [("bytes", c_u64), ("zero_bytes", c_u64), ("blocks", c_u64), ("unique_blocks", c_u64),
@@ -318,6 +335,11 @@ SIGNATURES = {
     "s3dg_npz_check_batch": (c_int, [c_vp, c_vp, ctypes.POINTER(NpzArchive), c_u64, ctypes.POINTER(NpzMember), c_u64,
                                      c_vp, c_u64, c_vp, ctypes.POINTER(NpzRec), ctypes.POINTER(NpzRec)]),
     "s3dg_npz_index_batch": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(NpzStream), c_u64, c_vp, ctypes.POINTER(NpzWalkRec)]),
+    "s3dg_inflate_batch": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(InflateItem), c_u64, c_vp,
+                                   ctypes.POINTER(InflateRec), ctypes.POINTER(InflateRec)]),
+    "s3dg_npz_zindex_batch": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(NpzStream), c_u64, c_vp, ctypes.POINTER(NpzWalkRec)]),
+    "s3dg_npz_zunpack_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(NpzTake), c_u64, c_vp,
+                                       ctypes.POINTER(NpzZUnpackRec), ctypes.POINTER(NpzZUnpackRec)]),
     "s3dg_npz_unpack_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(NpzTake), c_u64, c_vp,
                                       ctypes.POINTER(NpzUnpackRec), ctypes.POINTER(NpzUnpackRec)]),
     "s3dg_npz_unpack_timed": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(NpzTake), c_u64, c_vp,

@@ -38,7 +38,8 @@ SOURCES = [os.path.join(CSRC, "s3dg_ks_kernels.hip"), os.path.join(CSRC, "s3dg_b
            os.path.join(CSRC, "s3dg_chunk_search.hip"), os.path.join(CSRC, "s3dg_reduce.hip"),
            os.path.join(CSRC, "s3dg_reduce.cpp"),
            os.path.join(CSRC, "s3dg_npz_batch.hip"), os.path.join(CSRC, "s3dg_npz_batch.cpp"),
-           os.path.join(CSRC, "s3dg_npz_unpack.hip"), os.path.join(CSRC, "s3dg_npz_unpack.cpp")]
+           os.path.join(CSRC, "s3dg_npz_unpack.hip"), os.path.join(CSRC, "s3dg_npz_unpack.cpp"),
+           os.path.join(CSRC, "s3dg_inflate.hip"), os.path.join(CSRC, "s3dg_inflate.cpp")]
 HEADERS = [os.path.join(CSRC, "s3dg_internal.h"), os.path.join(CSRC, "s3dg_dev.h"),
            os.path.join(CSRC, "s3dg_ctx.h"),
            os.path.join(CSRC, "s3dg_batch_plan.h"), os.path.join(CSRC, "s3dg_ks_verify_plan.h"),
@@ -55,7 +56,7 @@ HEADERS = [os.path.join(CSRC, "s3dg_internal.h"), os.path.join(CSRC, "s3dg_dev.h
            os.path.join(CSRC, "s3dg_tfrecord_plan.h"), os.path.join(CSRC, "s3dg_tfrecord_var_plan.h"),
            os.path.join(CSRC, "s3dg_tfrecord_search_plan.h"), os.path.join(CSRC, "s3dg_tfrecord_extract_plan.h"),
            os.path.join(CSRC, "s3dg_npz_plan.h"), os.path.join(CSRC, "s3dg_npz_unpack_plan.h"),
-           os.path.join(CSRC, "s3dg_prefix.h"),
+           os.path.join(CSRC, "s3dg_inflate_plan.h"), os.path.join(CSRC, "s3dg_prefix.h"),
            os.path.join(ROOT, "include", "s3dlio_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
@@ -161,7 +162,8 @@ def compile_flags(root: str = ROOT) -> list[str]:
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"s3dg_tfrecord_search.hip": NO_PACKED_FP32, "s3dg_chunk_search.hip": NO_PACKED_FP32,
               "s3dg_reduce.hip": NO_PACKED_FP32, "s3dg_tfrecord_extract.hip": NO_PACKED_FP32,
-              "s3dg_npz_batch.hip": NO_PACKED_FP32, "s3dg_npz_unpack.hip": NO_PACKED_FP32}
+              "s3dg_npz_batch.hip": NO_PACKED_FP32, "s3dg_npz_unpack.hip": NO_PACKED_FP32,
+              "s3dg_inflate.hip": NO_PACKED_FP32}
 
 
 def build(force: bool = False, verbose: bool = False) -> str:

@@ -18,6 +18,7 @@
 #include "s3dg_tfrecord_extract_plan.h" // TfxCounts, TfxLayout: the extract's workspace
 #include "s3dg_npz_plan.h"          // NpzCounts, NpzLayout: the NPZ batch's workspace
 #include "s3dg_npz_unpack_plan.h"   // NzuCounts, NzuLayout: the NPZ unpack's workspace
+#include "s3dg_inflate_plan.h"      // InfWork, InfDevRes: the inflate's work items
 #include "s3dg_prefix.h"            // PrefixParams and the one function that makes them
 
 // Sets the calling thread's error text (s3dg_last_error) and returns code.
@@ -448,6 +449,16 @@ hipError_t npz_index_launch(const uint8_t *base, uint8_t *table, const s3dg_npz_
 hipError_t npz_unpack_launch(const uint8_t *src, const uint8_t *tab, uint8_t *dst, uint8_t *ws, const NzuLayout &L,
                              const NzuCounts &C, uint64_t n, size_t scan_tmp_bytes, void *tab_dev, int cus, hipEvent_t *marks,
                              hipStream_t s);
+// DEFLATE streams inflated, one wave per work item, and the CRC-32 of the
+// finished outputs (s3dg_inflate.hip; s3dg_inflate_plan.h).  The z walk is
+// npz_index_launch's accepting deflated members; the z unpack plans on the
+// device (one thread per take: verdicts, work items, results reset) and runs
+// the items.
+hipError_t inflate_launch(const InfWork *work_dev, uint64_t n, InfDevRes *res_dev, hipStream_t s);
+hipError_t npz_zindex_launch(const uint8_t *base, uint8_t *table, const s3dg_npz_stream *arch_dev, uint64_t n,
+                             s3dg_npz_walk_result *res_dev, hipStream_t s);
+hipError_t npz_zunpack_launch(const uint8_t *src, const uint8_t *tab, uint8_t *dst, const TfxTake *tk_dev, uint64_t n, uint64_t ents,
+                              InzDevTake *verdict_dev, InfWork *work_dev, InfDevRes *res_dev, hipStream_t s);
 
 // ---- NUMA placement of host buffers (s3dg_numa.cpp) -------------------------
 bool device_local_cpus(int device, cpu_set_t *out);

@@ -448,6 +448,69 @@ class NpzUnpack:
                    None if ft == none else ft, None if fm == none else fm, takes)
 
 
+INFLATE_OK, INFLATE_CAPACITY, INFLATE_SIZE, INFLATE_TRUNCATED, INFLATE_BAD_STREAM = range(5)
+_INFLATE_STATUS = ("ok", "capacity", "size", "truncated", "bad_stream")
+
+
+@dataclass(frozen=True)
+class InflateResult:
+    """What Context.inflate_batch did (s3dg_inflate_result): the totals over
+    the items (status: the worst of them) and, unless it was called with
+    per_item=False, one InflateResult per item."""
+    status: str = "ok"            # "ok" | "capacity" | "size" | "truncated" | "bad_stream"
+    out_bytes: int = 0            # bytes written
+    in_bytes: int = 0             # input bytes consumed
+    bad_crc: int = 0              # "ok" items whose output's CRC-32 differs from the one given
+    first_item: int | None = None     # the first item that is not "ok" or whose CRC differs
+    items: tuple | None = None
+
+    @property
+    def ok(self) -> bool:
+        return self.status == "ok" and self.bad_crc == 0
+
+    @classmethod
+    def _of(cls, r, items=None) -> "InflateResult":
+        fi = int(r.first_item)
+        return cls(_INFLATE_STATUS[int(r.status)], int(r.out_bytes), int(r.in_bytes), int(r.bad_crc),
+                   None if fi == 2**64 - 1 else fi, items)
+
+
+NpzZEntry = namedtuple("NpzZEntry", "local_off name_len flags data_off csize usize crc method")
+NpzZEntry.__doc__ = "One member as Context.npz_zindex_batch describes it; every offset from the archive's first byte."
+
+
+def npz_zentries(table, tab_off: int, count: int) -> list:
+    """Z entries [0, count) of the table at table + tab_off, copied back, as NpzZEntry tuples."""
+    raw = table[tab_off:tab_off + 32 * count].cpu().numpy().view("<u4").reshape(-1, 8)
+    return [NpzZEntry(int(e[0]), int(e[1]) & 0xFFFF, int(e[1]) >> 16, *(int(x) for x in e[2:7])) for e in raw]
+
+
+@dataclass(frozen=True)
+class NpzZUnpack:
+    """What Context.npz_zunpack_batch did (s3dg_npz_zunpack_result); the
+    fields of NpzUnpack, and bad_stream."""
+    members: int = 0
+    bytes: int = 0                # bytes the members' streams delivered
+    span: int = 0
+    status: str = "taken"         # "taken" | "capacity" | "table"
+    bad_crc: int = 0              # members delivered whole whose CRC-32 differs from the entry's
+    bad_stream: int = 0           # members whose stream is no DEFLATE stream of usize bytes
+    first_take: int | None = None
+    first_member: int | None = None
+    takes: tuple | None = None
+
+    @property
+    def ok(self) -> bool:
+        return self.status == "taken" and self.bad_crc == 0 and self.bad_stream == 0
+
+    @classmethod
+    def _of(cls, r, takes=None) -> "NpzZUnpack":
+        none = 2**64 - 1
+        ft, fm = int(r.first_take), int(r.first_member)
+        return cls(int(r.members), int(r.bytes), int(r.span), _UNPACK_STATUS[int(r.status)], int(r.bad_crc),
+                   int(r.bad_stream), None if ft == none else ft, None if fm == none else fm, takes)
+
+
 def _npz_members(members):
     """(s3dg_npz_member array, count, blob) of members (name, npy_header_bytes, src_off_or_None, size)."""
     rows = [tuple(m) for m in members]
@@ -1456,6 +1519,87 @@ class Context:
         call("s3dg_npz_unpack_batch", self._h, self._src(src, need_src), self._src(table, need_tab),
              self._dst(dst, need_dst), arr, n, self._s(stream), ctypes.byref(tot), per)
         return NpzUnpack._of(tot, tuple(NpzUnpack._of(per[k]) for k in range(n)) if per_take else None)
+
+    # -- DEFLATE streams and compressed NPZ members --------------------------------------
+    def inflate_batch(self, src, dst, items, stream=None, per_item: bool = True) -> InflateResult:
+        """Raw DEFLATE streams (RFC 1951, no zlib or gzip wrapper) inflated in
+        one device call, one wave per stream.  Each item is
+        (src_off, src_bytes, dst_off, dst_cap) with an optional want_bytes
+        (None: any size) and an optional crc (None: not checked): the stream
+        at src + src_off goes to dst + dst_off (a multiple of 16), at most
+        dst_cap bytes.  An item that fails ends with its status ("capacity",
+        "size", "truncated", "bad_stream"), keeps what it wrote inside its own
+        place and leaves the others untouched.  Synchronous on `stream`;
+        per_item=False asks for the totals only."""
+        rows = []
+        for it in items:
+            it = tuple(it) + (None, None)[:max(0, 6 - len(it))]
+            if len(it) != 6:
+                raise ValueError("an item is (src_off, src_bytes, dst_off, dst_cap[, want_bytes[, crc]])")
+            rows.append(it)
+        n = len(rows)
+        arr = (_lib.InflateItem * max(1, n))()
+        need_src = need_dst = 0
+        for k, (so, sb, do, dc, want, crc) in enumerate(rows):
+            if any(int(x) < 0 or int(x) >= 2**64 for x in (so, sb, do, dc)):
+                raise ValueError("item fields must fit 64 unsigned bits")
+            arr[k] = _lib.InflateItem(int(so), int(sb), int(do), int(dc), 2**64 - 1 if want is None else int(want),
+                                      0 if crc is None else int(crc) & 0xFFFFFFFF, 0 if crc is None else 1)
+            need_src = max(need_src, int(so) + int(sb))
+            need_dst = max(need_dst, int(do) + int(dc))
+        tot = _lib.InflateRec(0, 0, 0, 0, 2**64 - 1)
+        per = (_lib.InflateRec * max(1, n))() if per_item else None
+        call("s3dg_inflate_batch", self._h, self._src(src, need_src), self._dst(dst, need_dst), arr, n, self._s(stream),
+             ctypes.byref(tot), per)
+        return InflateResult._of(tot, tuple(InflateResult._of(per[k]) for k in range(n)) if per_item else None)
+
+    def npz_zindex_batch(self, src, archives, table, stream=None) -> list:
+        """npz_index_batch for archives whose members are stored or deflated
+        (numpy.savez_compressed's included): the same arguments and NpzWalk
+        results, with 32-byte z entries that describe each member's whole
+        stored file (npz_zentries reads them back)."""
+        rows = [tuple(int(x) for x in a) for a in archives]
+        if any(len(a) != 4 for a in rows):
+            raise ValueError("an archive is (off, nbytes, tab_off, max_members)")
+        if any(x < 0 or x >= 2**64 for a in rows for x in a):
+            raise ValueError("archive fields must fit 64 unsigned bits")
+        n = len(rows)
+        arr = (_lib.NpzStream * max(1, n))()
+        need_src = need_tab = 0
+        for k, (off, nbytes, tab_off, cap) in enumerate(rows):
+            arr[k] = _lib.NpzStream(off, nbytes, tab_off, cap)
+            need_src = max(need_src, off + nbytes)
+            need_tab = max(need_tab, tab_off + 32 * min(cap, 65535))
+        res = (_lib.NpzWalkRec * max(1, n))()
+        call("s3dg_npz_zindex_batch", self._h, self._src(src, need_src), self._dst(table, need_tab), arr, n, self._s(stream), res)
+        return [NpzWalk._of(res[k]) for k in range(n)]
+
+    def npz_zunpack_batch(self, src, table, dst, takes, stream=None, per_take: bool = True) -> NpzZUnpack:
+        """npz_unpack_batch over z entries: member i's whole stored file (NPY
+        header and array bytes) lands at dst + dst_off + the sum of
+        round_up(usize_j, 16) over the members before it, a stored member
+        copied and a deflated one inflated on the device, every CRC-32
+        checked.  Takes as npz_unpack_batch's; "table" and "capacity" takes
+        write nothing."""
+        rows = [tuple(int(x) for x in tk) for tk in takes]
+        if any(len(tk) != 7 for tk in rows):
+            raise ValueError("a take is (off, bytes, tab_off, first, count, dst_off, dst_cap)")
+        if any(x < 0 or x >= 2**64 for tk in rows for x in tk):
+            raise ValueError("take fields must fit 64 unsigned bits")
+        n = len(rows)
+        arr = (_lib.NpzTake * max(1, n))()
+        need_src = need_tab = need_dst = 0
+        for k, tk in enumerate(rows):
+            arr[k] = _lib.NpzTake(*tk)
+            off, nbytes, tab_off, first, count, dst_off, dst_cap = tk
+            need_src = max(need_src, off + nbytes)
+            need_tab = max(need_tab, tab_off + 32 * (first + count))
+            need_dst = max(need_dst, dst_off + dst_cap)
+        tot = _lib.NpzZUnpackRec(0, 0, 0, 0, 0, 0, 2**64 - 1, 2**64 - 1)
+        per = (_lib.NpzZUnpackRec * max(1, n))() if per_take else None
+        call("s3dg_npz_zunpack_batch", self._h, self._src(src, need_src), self._src(table, need_tab),
+             self._dst(dst, need_dst), arr, n, self._s(stream), ctypes.byref(tot), per)
+        return NpzZUnpack._of(tot, tuple(NpzZUnpack._of(per[k]) for k in range(n)) if per_take else None)
 
     def npz_list(self, src, off: int, nbytes: int, stream=None) -> list:
         """list_npz_arrays for one archive of nbytes at src + off: [(name,
